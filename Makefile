@@ -52,11 +52,11 @@ conformance-clean:
 coverage: build  ## line coverage of the CPU suite per component (tools/coverage.py → coverage.json)
 	$(PYTHON) tools/coverage.py --flag kf=78 --flag odh=85 --flag runtime=84 --flag apiserver=85
 
-bench: build  ## headline benchmark on one MI355X
-	$(PYTHON) bench.py
+bench: build  ## headline benchmark on one MI355X, with every block beside it (--full)
+	$(PYTHON) bench.py --full
 
 bench-8: build  ## one control-plane shard per MI355X of an 8-GPU node
-	$(PYTHON) -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+	$(PYTHON) -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --full --gpus 8
 
 manifests:  ## regenerate the kustomize tree under config/
 	$(PYTHON) -m odh_kubeflow_amd.deploy.manifests --out config

@@ -15,8 +15,13 @@ One *step* is one full notebook lifecycle per rank (one rank per MI355X of the n
 The control plane is the shipped process(es) (``--arch sharded``: ``cmd/control_plane.py
 --shard r`` per rank; ``--arch unsharded``: one ``cmd/kf_manager.py`` + one
 ``cmd/odh_manager.py`` for every rank's notebooks).  The Ready path is the default
-deployment's: no start-up probe (``amd.com/gpu-probe`` is opt-in); a few probe notebooks
-run after the timed region and are reported on their own (``gpu_probe_init_container``).
+deployment's: no start-up probe (``amd.com/gpu-probe`` is opt-in).
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the K
+steps and prints the result line (``--dump-outputs DIR``: and writes what the last timed step
+produced).  ``--full`` adds everything measured beside it, untimed: the in-process
+(envtest-style) figure, the RCCL check, a few probe notebooks (``gpu_probe_init_container``),
+the ``burst``, ``resident`` and ``storage`` blocks and the BASELINE configs #2-#5.
 
 ``value`` = reconciles completed by the notebook controllers inside the K timed steps ÷ the
 timed wall time (whole job).  Weak scaling: N notebooks in flight on N GPUs.  The figure
@@ -136,7 +141,19 @@ def parse(argv=None):
                         "on every apiserver write (reported in 'storage'; 0: skip)")
     p.add_argument("--storage-ms", type=float, default=2.0, help="the storage block's per-write latency")
     p.add_argument("--json-out", default=None)
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline too: the in-process (envtest-style) figure, the RCCL "
+                        "check, the start-up probe sample, the burst, resident and storage blocks and the "
+                        "BASELINE configs #2-#5 (each still has its own switch); without it a run sets up, "
+                        "warms up, times the steps and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps: what the last timed step produced (the Ready Notebook and its "
+                        "pod, see lifecycle_outputs) as DIR/<name>.npy, float64")
+    args = p.parse_args(argv)
+    if not args.full:  # the headline alone: nothing that takes a run (or a block after the window) of its own
+        args.no_inprocess_baseline = args.no_configs = args.no_gpu_probe = True
+        args.burst = args.resident = args.storage_steps = 0
+    return args
 
 
 def pct(xs, q):
@@ -147,6 +164,83 @@ def pct(xs, q):
     lo = int(k)
     hi = min(lo + 1, len(xs) - 1)
     return xs[lo] + (xs[hi] - xs[lo]) * (k - lo)
+
+
+# set by the apiserver or by the clock, different in every run: left out of the dumped outputs
+VOLATILE_KEYS = frozenset((
+    "uid", "resourceVersion", "creationTimestamp", "deletionTimestamp", "managedFields", "generation", "selfLink",
+    "startTime", "startedAt", "finishedAt", "lastTransitionTime", "lastProbeTime", "lastHeartbeatTime", "containerID",
+    "observedGeneration"))
+
+
+def _stable(o):
+    """``o`` without the fields of VOLATILE_KEYS, keys sorted (lists keep their order: it is
+    part of what the controllers wrote)."""
+    if isinstance(o, dict):
+        return {k: _stable(v) for k, v in sorted(o.items()) if k not in VOLATILE_KEYS}
+    if isinstance(o, list):
+        return [_stable(v) for v in o]
+    return o
+
+
+def _json_bytes(o):
+    import numpy as np
+
+    text = json.dumps(_stable(o), sort_keys=True, separators=(",", ":"))
+    return np.frombuffer(text.encode(), dtype=np.uint8).astype(np.float64)
+
+
+def lifecycle_outputs(notebook, pod) -> dict:
+    """What a caller of one timed step receives — the Notebook as it turned Ready and its pod —
+    as float64 arrays, the same from run to run (names and namespaces follow from the step
+    number; VOLATILE_KEYS and the Notebook's annotations, where the culler keeps its clock,
+    are left out):
+
+    * ``notebook_summary``: readyReplicas, Ready condition True, conditions, containers and
+      volumes of the (mutated) pod template;
+    * ``pod_summary``: Ready condition True, phase Running, containers, init containers,
+      volumes, ``amd.com/gpu`` limit of the first container, the allocated GPU indices
+      (``amd.com/gpu-ids``, padded with -1 to the node's 8);
+    * ``notebook_json`` / ``pod_json``: the UTF-8 bytes of the canonical JSON of the Notebook's
+      labels, spec and status and of the pod's labels, annotations, spec and status, so that
+      two builds can be compared field for field (``bytes(a.astype('uint8'))`` reads it back)."""
+    import numpy as np
+
+    nb, pod = notebook or {}, pod or {}
+
+    def cond(o, typ):
+        return float(any(c.get("type") == typ and c.get("status") == "True"
+                         for c in (o.get("status") or {}).get("conditions") or []))
+
+    tmpl = (((nb.get("spec") or {}).get("template") or {}).get("spec") or {})
+    nst = nb.get("status") or {}
+    pspec, pst, pmeta = pod.get("spec") or {}, pod.get("status") or {}, pod.get("metadata") or {}
+    ctrs = pspec.get("containers") or []
+    limit = ((ctrs[0].get("resources") or {}).get("limits") or {}).get("amd.com/gpu", 0) if ctrs else 0
+    ids = [float(x) for x in str((pmeta.get("annotations") or {}).get("amd.com/gpu-ids", "")).split(",")
+           if x.strip().lstrip("-").isdigit()][:8]
+    nmeta = nb.get("metadata") or {}
+    return {
+        "notebook_summary": np.array([float(nst.get("readyReplicas") or 0), cond(nb, "Ready"),
+                                      float(len(nst.get("conditions") or [])), float(len(tmpl.get("containers") or [])),
+                                      float(len(tmpl.get("volumes") or []))], dtype=np.float64),
+        "pod_summary": np.array([cond(pod, "Ready"), float(pst.get("phase") == "Running"), float(len(ctrs)),
+                                 float(len(pspec.get("initContainers") or [])), float(len(pspec.get("volumes") or [])),
+                                 float(limit), *ids, *([-1.0] * (8 - len(ids)))], dtype=np.float64),
+        "notebook_json": _json_bytes({"labels": nmeta.get("labels"), "spec": nb.get("spec"), "status": nst}),
+        "pod_json": _json_bytes({"labels": pmeta.get("labels"), "annotations": pmeta.get("annotations"),
+                                 "spec": pspec, "status": pst}),
+    }
+
+
+def dump_outputs(directory: str, per_rank: list) -> None:
+    """``DIR/<name>.npy``: the last timed step's outputs, one rank's after the other's."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name in sorted({k for o in per_rank for k in o}):
+        parts = [np.asarray(o[name], dtype=np.float64) for o in per_rank if name in o]
+        np.save(os.path.join(directory, f"{name}.npy"), np.concatenate(parts) if parts else np.zeros(0))
 
 
 async def run_local(args, n_gpus: int) -> dict:
@@ -160,6 +254,7 @@ async def run_local(args, n_gpus: int) -> dict:
                         env={"SET_PIPELINE_RBAC": "false", "SET_PIPELINE_SECRET": "false"})
     lat_ms, teardown_ms = [], []
     recon = 0
+    last = {}  # the last timed step's Ready notebooks and their pods (--dump-outputs)
     async with LocalCluster(cfg) as cl:
         await cl.ensure_namespace("bench")
         step_id = 0
@@ -189,6 +284,9 @@ async def run_local(args, n_gpus: int) -> dict:
                     await asyncio.sleep(0.0005)
             if pending:
                 raise RuntimeError(f"notebooks not Ready: {sorted(pending)}")
+            if timed and args.dump_outputs and step_id == args.warmup + args.steps:
+                last.update({nm: (cl.store.peek(kinds.NOTEBOOK, nm, "bench"), cl.store.peek(kinds.POD, f"{nm}-0", "bench"))
+                             for nm in names})
             t_del = time.perf_counter()
             await asyncio.gather(*(cl.admin.delete(kinds.NOTEBOOK, nm, "bench") for nm in names))
             ok = await cl.wait_for(lambda: all(cl.store.peek(kinds.NOTEBOOK, nm, "bench") is None and
@@ -220,7 +318,8 @@ async def run_local(args, n_gpus: int) -> dict:
         await cl.settle(5)  # untimed: the per-lifecycle count includes them
         breakdown = breakdown_delta(b0, cl.reconcile_breakdown())
     return {"elapsed": elapsed, "reconciles": recon, "lat_ms": lat_ms, "odh": use_odh,
-            "teardown_ms": teardown_ms, "breakdown": breakdown}
+            "teardown_ms": teardown_ms, "breakdown": breakdown,
+            "outputs": [lifecycle_outputs(nb, pod) for _nm, (nb, pod) in sorted(last.items())]}
 
 
 def breakdown_delta(b0: dict, b1: dict) -> dict:
@@ -289,7 +388,7 @@ def main(argv=None):
                 "value", "ms_per_step", "p50_ready_ms", "p95_ready_ms", "notebooks_ready_per_s",
                 "reconciles_per_notebook", "p50_teardown_ms")}
     else:
-        out = _run_inprocess(args, n)
+        out = _run_inprocess(args, n, dump=True)
     if rank == 0 and out is not None and n == 1 and not args.no_configs:
         out["configs"] = run_configs(args)
     if rank == 0 and out is not None:
@@ -351,9 +450,11 @@ def run_configs(args) -> dict:
     return out
 
 
-def _run_inprocess(args, n: int) -> dict:
+def _run_inprocess(args, n: int, dump: bool = False) -> dict:
     """One process: every controller, the webhook and the kubelet stand-ins share the object store."""
     res = asyncio.run(run_local(args, n))
+    if dump and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"])
     out = report(args, n, res)
     out["config"]["architecture"] = "inprocess"
     return out

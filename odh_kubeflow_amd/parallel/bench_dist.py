@@ -167,7 +167,12 @@ def measure(args) -> Optional[dict]:
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     if ndev:
         torch.cuda.set_device(local_rank % ndev)
-    rccl_ms = _rccl_check(torch, dist, local_rank) if ndev else None
+    rccl_ms = _rccl_check(torch, dist, local_rank) if ndev and getattr(args, "full", True) else None
+    if ndev and rccl_ms is None:
+        # the GPU context is created here, as the RCCL check creates it: the first
+        # torch.cuda.synchronize() would otherwise pay for it between warm-up and window,
+        # with every control-plane process idle meanwhile
+        torch.cuda.synchronize()
     probe_sample = 0 if (args.no_gpu_probe or not ndev) else max(0, args.probe_sample)
     res = asyncio.run(_main(args, dist, torch, rank, world, ndev, probe_sample))
     out = None
@@ -175,6 +180,10 @@ def measure(args) -> Optional[dict]:
         from bench import report  # noqa: E402  (bench.py is the entry point on sys.path)
 
         out = report(args, world, res)
+        if getattr(args, "dump_outputs", None):
+            from bench import dump_outputs  # noqa: E402
+
+            dump_outputs(args.dump_outputs, res.get("outputs") or [])
         arch = args.arch if args.arch in ("sharded", "unsharded") else "sharded"
         if arch == "sharded" and getattr(args, "single_process_shard", False):
             out["config"]["parallelism"] = (f"namespace-sharded control plane x{world}: one `cmd/control_plane.py "
@@ -947,9 +956,9 @@ def _prof_per_step(p0: Optional[dict], p1: Optional[dict], steps: int) -> Option
 
 
 async def _lifecycle(shard, nm: str, ann: Optional[dict], timeout: float = 120.0,
-                     ns: Optional[str] = None) -> tuple:
+                     ns: Optional[str] = None, keep: Optional[dict] = None) -> tuple:
     """create → Ready → delete → gone in ``ns`` (default: the rank's first namespace);
-    returns (create→Ready s, Ready→gone s, the pod)."""
+    returns (create→Ready s, Ready→gone s, the pod).  ``keep``: receives the Ready Notebook."""
     from ..models import kinds
     from ..models.notebook import notebook
 
@@ -960,6 +969,8 @@ async def _lifecycle(shard, nm: str, ann: Optional[dict], timeout: float = 120.0
         raise RuntimeError(f"notebook {ns}/{nm} not Ready")
     ready = time.perf_counter()
     pod = shard.peek(kinds.POD, f"{nm}-0", ns)
+    if keep is not None:
+        keep["notebook"] = shard.peek(kinds.NOTEBOOK, nm, ns)
     await shard.admin.delete(kinds.NOTEBOOK, nm, ns)
     if not await shard.wait_until(lambda: shard.gone(nm, ns), 60):
         raise RuntimeError(f"teardown of {ns}/{nm} did not finish")
@@ -1039,10 +1050,17 @@ async def _drive(args, shard, dist, torch, children: Optional[dict] = None, nati
     nss = shard.cfg.user_namespaces
     ns_counts = {ns: 0 for ns in nss}  # timed notebooks per namespace
 
+    last: dict = {}  # the last timed step's Ready notebook and its pod (--dump-outputs)
+    want_outputs = bool(getattr(args, "dump_outputs", None))
+
     async def one_step(timed: bool):
         state["step"] += 1
         ns = nss[state["step"] % len(nss)]
-        ready_s, gone_s, _pod = await _lifecycle(shard, f"nb-s{state['step']}", dict(base_ann) or None, ns=ns)
+        keep = last if timed and want_outputs and state["step"] == args.warmup + args.steps else None
+        ready_s, gone_s, pod = await _lifecycle(shard, f"nb-s{state['step']}", dict(base_ann) or None, ns=ns,
+                                                keep=keep)
+        if keep is not None:
+            keep["pod"] = pod
         if timed:
             lat_ms.append(ready_s * 1e3)
             teardown_ms.append(gone_s * 1e3)
@@ -1172,6 +1190,11 @@ async def _drive(args, shard, dist, torch, children: Optional[dict] = None, nati
     # the first steps of the window run slower than the rest (warm-up of the host, not the code)
     life = [a + b for a, b in zip(lat_ms, teardown_ms)]
     blocks = [round(statistics.fmean(life[i:i + 20]), 3) for i in range(0, len(life), 20)]
+    outputs = None
+    if last:
+        from bench import lifecycle_outputs  # noqa: E402  (bench.py is the entry point)
+
+        outputs = lifecycle_outputs(last.get("notebook"), last.get("pod"))
     trace = os.environ.get("ODH_BENCH_STEP_TRACE")  # debug aid: every timed step's two halves
     if trace:
         with open(f"{trace}.{dist.get_rank()}.json", "w") as f:
@@ -1181,7 +1204,8 @@ async def _drive(args, shard, dist, torch, children: Optional[dict] = None, nati
                                                         "cpu": cpu, "rss": rss, "in_window": in_window,
                                                         "settled": settled, "idle": idle, "probe": samples,
                                                         "io": io, "snap_lag_ms": snap_lag * 1e3,
-                                                        "ns_counts": ns_counts, "owner": owner})
+                                                        "ns_counts": ns_counts, "owner": owner,
+                                                        "outputs": outputs})
     per_step = 1e3 / max(1, args.steps)
     cpu_ms = {"ranks": [round(g["cpu"]["rank"] * per_step, 3) for g in gathered]}
     for g in gathered:
@@ -1207,6 +1231,7 @@ async def _drive(args, shard, dist, torch, children: Optional[dict] = None, nati
             "apiserver_profile_per_step": prof, "breakdown": merge_breakdowns(g["settled"] for g in gathered),
             "quiesced": all(g["idle"] for g in gathered),
             "io_per_notebook": io_per_notebook([g["io"] for g in gathered], args.steps * len(gathered)),
+            "outputs": [g["outputs"] for g in gathered if g.get("outputs")],
             "burst": burst, "shard_load": load, "resident": resident, "storage": storage,
             "recon_snapshot_lag_ms": round(max(g["snap_lag_ms"] for g in gathered), 3),
             "probe_sample": [s for g in gathered for s in g["probe"]],

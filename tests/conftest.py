@@ -13,6 +13,25 @@ def pytest_configure(config):
 
 
 @pytest.fixture
+def sock_dir(tmp_path):
+    """A directory for unix sockets.  ``sun_path`` holds 107 bytes, and ``tmp_path`` (under
+    ``$TMPDIR``, the test name in it) can be longer than that: then a short directory under
+    ``/tmp`` is used instead, removed afterwards."""
+    if len(os.fsencode(str(tmp_path))) <= 80:
+        yield tmp_path
+        return
+    import pathlib
+    import shutil
+    import tempfile
+
+    d = tempfile.mkdtemp(prefix="odh-", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
 def run():
     """Run a coroutine to completion on a fresh event loop."""
     def _run(coro, timeout=60):

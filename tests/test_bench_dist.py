@@ -23,8 +23,8 @@ def _port():
 
 def test_bench_two_ranks_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-gpu-probe"]
+           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--full", "--gpus", "2", "--steps", "3",
+           "--warmup", "1", "--no-gpu-probe"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -47,12 +47,43 @@ def test_bench_two_ranks_gloo():
 
 
 def test_bench_single_process_contract():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-gpu-probe"], cwd=ROOT,
-                         capture_output=True, text=True, timeout=240)
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-gpu-probe"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["config"]["odh_webhook_path"] is True
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without ``--full``: the timed steps and the result line, none of the blocks measured
+    beside them.  ``--dump-outputs``: the last timed step's Ready Notebook and pod as float64
+    arrays, identical from run to run (two builds are compared output for output)."""
+    import numpy as np
+
+    runs = []
+    for i in (0, 1):
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / str(i))], cwd=ROOT, capture_output=True, text=True,
+                             timeout=240)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "reconciles/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "n/a"
+        assert not {"inprocess_n1", "configs", "burst", "resident", "gpu_probe_init_container",
+                    "rccl_allreduce_check_ms"} & set(d) and not [k for k in d if k.startswith("storage_")]
+        runs.append({f: np.load(tmp_path / str(i) / f) for f in sorted(os.listdir(tmp_path / str(i)))})
+    a, b = runs
+    assert sorted(a) == ["notebook_json.npy", "notebook_summary.npy", "pod_json.npy", "pod_summary.npy"]
+    for f in a:
+        assert a[f].dtype == np.float64 and a[f].shape == b[f].shape and (a[f] == b[f]).all(), f
+    assert sum(x.nbytes for x in a.values()) < 64 << 20
+    # readyReplicas 1 and Ready; the pod Ready and Running, one amd.com/gpu, on GPU 0 (first free)
+    assert a["notebook_summary.npy"][:2].tolist() == [1.0, 1.0]
+    assert a["pod_summary.npy"][[0, 1, 5, 6]].tolist() == [1.0, 1.0, 1.0, 0.0]
+    pod = json.loads(bytes(a["pod_json.npy"].astype(np.uint8)))
+    assert pod["spec"]["hostname"] == "nb-s4-0"  # the last of 1 warm-up + 3 timed steps
+    assert pod["spec"]["containers"][0]["resources"]["limits"]["amd.com/gpu"] == "1"
 
 
 def test_bench_reference_emulation_serialises():
@@ -106,8 +137,8 @@ def test_bench_namespaces_per_rank_assigned_by_the_shard_hash():
     from odh_kubeflow_amd.parallel.bench_dist import bench_namespaces
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "8", "--warmup", "1",
-           "--no-gpu-probe", "--namespaces-per-rank", "4", "--burst", "4", "--burst-rounds", "1",
+           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--full", "--gpus", "2", "--steps", "8",
+           "--warmup", "1", "--no-gpu-probe", "--namespaces-per-rank", "4", "--burst", "4", "--burst-rounds", "1",
            "--resident", "16", "--resident-window", "1", "--resident-steps", "2"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]

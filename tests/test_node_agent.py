@@ -54,8 +54,8 @@ def test_podresources_codec_roundtrip():
     assert pr.decode_list_response(extra)[0].containers[0].name == "c"
 
 
-def test_podresources_grpc_list(tmp_path):
-    sock = str(tmp_path / "kubelet.sock")
+def test_podresources_grpc_list(sock_dir):
+    sock = str(sock_dir / "kubelet.sock")
     srv = FakePodResourcesServer(sock).start()
     try:
         srv.assign("user", "nb-0", "nb", "amd.com/gpu", [fake_bdf(3)])
@@ -100,9 +100,9 @@ def test_device_resolver_bdf_partitions(tmp_path):
         tel.close()
 
 
-def test_attribution_sources(run, sysfs, tmp_path):
+def test_attribution_sources(run, sysfs, tmp_path, sock_dir):
     root, proc, _minors, tel = sysfs
-    sock = str(tmp_path / "pr.sock")
+    sock = str(sock_dir / "pr.sock")
     srv = FakePodResourcesServer(sock).start()
     cp = CheckpointWriter(str(tmp_path / "dp" / "kubelet_internal_checkpoint"))
     try:
@@ -137,12 +137,12 @@ def test_attribution_sources(run, sysfs, tmp_path):
         srv.stop()
 
 
-def test_pod_resources_socket_that_appears_later_is_used(run, sysfs, tmp_path):
+def test_pod_resources_socket_that_appears_later_is_used(run, sysfs, sock_dir):
     """The kubelet socket is re-checked on every refresh: an agent started before the kubelet
     mounted it switches to the pod-resources API as soon as it appears (and reports it gone
     when it disappears), instead of losing that source for its whole lifetime."""
     _root, _proc, _minors, tel = sysfs
-    sock = str(tmp_path / "late.sock")
+    sock = str(sock_dir / "late.sock")
 
     async def go():
         att = Attributor(tel, pod_resources=pr.PodResourcesClient(sock, timeout_s=0.5), ttl_s=0.0)

@@ -75,20 +75,52 @@ def _kfd_listing() -> str:
 def gpu_state():
     """This process's KFD entry, found the way a node agent must find it: KFD names processes by
     their host PID (``/sys/class/kfd/kfd/proc/<pid>``), which differs from ``os.getpid()`` inside
-    a container — so the entry is the one whose VRAM grows by the 1 GiB this fixture allocates."""
+    a container — so the entry is the one whose VRAM grows by the 1 GiB this fixture allocates.
+
+    The node may be shared: another tenant's process can start, or grow by a GiB, between the
+    two readings — another checkout's run of this very test does.  So an entry must have been
+    listed before the allocation (this process was: it had initialised the GPU), and while more
+    than one entry qualifies, the allocation is released and made again with a size drawn at
+    random: only this process's entry shrinks, and then grows by that size."""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a visible MI355X")
+    import random
+
     from odh_kubeflow_amd.ops.telemetry import Telemetry
 
     torch.zeros(1, device="cuda:0")
     torch.cuda.synchronize()
     tel = Telemetry("/sys")
-    before = {(p.pid, p.gpu_id): p.vram_bytes for p in tel.kfd_processes("/proc")}
-    hold = torch.empty((1 << 30) // 4 + (64 << 20), dtype=torch.float32, device="cuda:0")  # > 1 GiB, resident
-    hold.fill_(1.0)
-    torch.cuda.synchronize()
-    after = tel.kfd_processes("/proc")
-    mine = [p for p in after if p.vram_bytes - before.get((p.pid, p.gpu_id), 0) >= (1 << 30)]
+    gib = 1 << 30
+
+    def read():
+        procs = tel.kfd_processes("/proc")
+        return procs, {(p.pid, p.gpu_id): p.vram_bytes for p in procs}
+
+    def allocate(extra_bytes=0):
+        t = torch.empty(gib // 4 + (64 << 20) + extra_bytes // 4, dtype=torch.float32, device="cuda:0")  # > 1 GiB, resident
+        t.fill_(1.0)
+        torch.cuda.synchronize()
+        return t
+
+    _procs, before = read()
+    hold = allocate()
+    after, held = read()
+    keys = {k for k, v in held.items() if k in before and v - before[k] >= gib}
+    for _ in range(3):
+        if len(keys) <= 1:
+            break
+        del hold
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        _procs, released = read()
+        keys = {k for k in keys if k in released and held[k] - released[k] >= gib}
+        hold = allocate(random.randrange(1, 256) * (4 << 20))
+        after, held = read()
+        size = hold.numel() * hold.element_size()
+        # the allocator's rounding and the driver's page size stay far below 64 MiB
+        keys = {k for k in keys if k in held and 0 <= held[k] - released[k] - size <= 64 << 20}
+    mine = [p for p in after if (p.pid, p.gpu_id) in keys]
     yield {"hold": hold, "tel": tel, "mine": mine, "devs": tel.devices(), "after": after}
     tel.close()
 
@@ -107,7 +139,7 @@ def test_kfd_lists_this_process_on_torchs_gpu(gpu_state):
         assert dev.pci_bdf.lower() == bdf.lower(), (dev.pci_bdf, bdf)
 
 
-def test_node_agent_process_on_the_mi355x(gpu_state, tmp_path):
+def test_node_agent_process_on_the_mi355x(gpu_state, tmp_path, sock_dir):
     from odh_kubeflow_amd.ops.gpu import LoadGenerator
     from odh_kubeflow_amd.testing.kubelet.podresources_server import FakePodResourcesServer
 
@@ -127,7 +159,7 @@ def test_node_agent_process_on_the_mi355x(gpu_state, tmp_path):
     token = "s3cret-" + uuid.uuid4().hex
     tok = tmp_path / "token"
     tok.write_text(token)
-    sock = str(tmp_path / "kubelet.sock")
+    sock = str(sock_dir / "kubelet.sock")
     srv = FakePodResourcesServer(sock).start()
     srv.assign("team", "nb-0", "nb", "amd.com/gpu", [bdf])
     port = _port()

@@ -29,13 +29,13 @@ while [ $# -gt 0 ]; do
     driver)
       n=$1; shift
       for i in $(seq 1 "$n"); do
-        timeout -k 10 420 python bench.py --gpus 1 --steps 20 --warmup 5 --json-out "$out/driver_$i.json" \
+        timeout -k 10 420 python bench.py --full --gpus 1 --steps 20 --warmup 5 --json-out "$out/driver_$i.json" \
           > "$out/driver_$i.log" 2>&1 || { echo "driver run $i failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
         python tools/summarize_bench.py "$out/driver_$i.log" | tee -a "$out/SUMMARY.txt"
       done ;;
     long)
       steps=$1; shift
-      timeout -k 10 600 python bench.py --gpus 1 --steps "$steps" --warmup 10 --no-configs --burst 0 --resident 0 \
+      timeout -k 10 600 python bench.py --full --gpus 1 --steps "$steps" --warmup 10 --no-configs --burst 0 --resident 0 \
         --json-out "$out/long_$steps.json" > "$out/long_$steps.log" 2>&1 \
         || { echo "long run failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
       python tools/summarize_bench.py "$out/long_$steps.log" | tee -a "$out/SUMMARY.txt" ;;
@@ -43,7 +43,7 @@ while [ $# -gt 0 ]; do
       # resident R K: R notebooks at rest, the culler writing its check stamp every K-th check
       r=$1; k=$2; shift 2
       f="$out/resident_${r}_k${k}_p${CULLING_PERIOD:-1}_$(date +%s)"
-      timeout -k 10 900 python bench.py --gpus 1 --steps 100 --warmup 10 --no-configs --burst 0 --storage-steps 0 \
+      timeout -k 10 900 python bench.py --full --gpus 1 --steps 100 --warmup 10 --no-configs --burst 0 --storage-steps 0 \
         --no-gpu-probe --resident "$r" --culler-stamp-every "$k" --resident-window 5 --resident-steps 40 \
         --culling-period "${CULLING_PERIOD:-1}" \
         --json-out "$f.json" > "$f.log" 2>&1 || { echo "resident run failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
@@ -53,7 +53,7 @@ while [ $# -gt 0 ]; do
       # path hop by hop of the timed (empty-cluster) notebooks and of those created on top
       r=$1; k=$2; shift 2
       f="$out/rescp_${r}_k${k}"
-      DEBUG_WRITE_AUDITLOG=$PWD/$f.audit.jsonl timeout -k 10 900 python bench.py --gpus 1 --steps 100 --warmup 10 \
+      DEBUG_WRITE_AUDITLOG=$PWD/$f.audit.jsonl timeout -k 10 900 python bench.py --full --gpus 1 --steps 100 --warmup 10 \
         --no-configs --burst 0 --storage-steps 0 --no-gpu-probe --resident "$r" --culler-stamp-every "$k" \
         --resident-window 5 --resident-steps 40 --json-out "$f.json" > "$f.log" 2>&1 \
         || { echo "rescp run failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
@@ -113,7 +113,7 @@ PY
       extra=(); [ "$arch" = unsharded ] && extra=(--arch unsharded)
       [ "$arch" = workers ] && extra=(--arch unsharded --workers 4 --kf-split-workers --webhook-replicas 3 --cache-configmaps)
       f="$out/burst${k}_$arch"
-      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-configs --no-gpu-probe --resident 0 \
+      timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-configs --no-gpu-probe --resident 0 \
         --storage-steps 0 --burst "$k" "${extra[@]}" --json-out "$f.json" > "$f.log" 2>&1 \
         || { echo "burst $k $arch failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
       python tools/summarize_bench.py "$f.log" | tee -a "$out/SUMMARY.txt" ;;
@@ -189,7 +189,7 @@ PY
       cl="$1"; wl="$2"; side="$3"; shift 3
       extra=(); [ "$cl" = openshift ] && extra+=(--openshift-pull-secret-ms 200)
       if [ "$side" = ref ]; then extra+=(--reference-emulation --steps 2 --warmup 1); else extra+=(--steps 20 --warmup 3); fi
-      timeout -k 10 400 python bench.py --burst 8 --burst-rounds 2 --resident 0 --storage-steps 0 --no-configs \
+      timeout -k 10 400 python bench.py --full --burst 8 --burst-rounds 2 --resident 0 --storage-steps 0 --no-configs \
         --no-gpu-probe --write-latency-ms "$wl" "${extra[@]}" > "$out/fair_${side}_${cl}_wl$wl.log" 2>&1 \
         || { echo "fair $cl $wl $side failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
       python - "$out/fair_${side}_${cl}_wl$wl.log" <<'PY' | tee -a "$out/SUMMARY.txt"
@@ -203,7 +203,7 @@ PY
       # burstdebug WL: burstcp with asyncio debug (callbacks over 100 ms logged) and every child's
       # stderr kept under $out/children
       wl="$1"; shift
-      PYTHONASYNCIODEBUG=1 ODH_CHILD_STDERR_DIR=$PWD/$out/children timeout -k 10 300 python bench.py --steps 5 --warmup 2 \
+      PYTHONASYNCIODEBUG=1 ODH_CHILD_STDERR_DIR=$PWD/$out/children timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 \
         --burst 8 --burst-rounds 2 --resident 0 --storage-steps 0 --no-configs --no-gpu-probe --write-latency-ms "$wl" \
         > "$out/burstdebug_wl$wl.log" 2>&1 || { echo "burstdebug failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
       python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{\"metric\"')][-1]); print(sys.argv[1], d['burst'].get('rounds'))" \
@@ -213,7 +213,7 @@ PY
       # burstcp WL: 8 at once (second of two bursts) at WL ms per apiserver write, with the audit
       # log: the burst notebooks' critical path, and the log itself (gzip) for the timeline
       wl="$1"; shift
-      DEBUG_WRITE_AUDITLOG=$PWD/$out/burst_wl$wl.audit.jsonl timeout -k 10 300 python bench.py --steps 5 --warmup 2 \
+      DEBUG_WRITE_AUDITLOG=$PWD/$out/burst_wl$wl.audit.jsonl timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 \
         --burst 8 --burst-rounds 2 --resident 0 --storage-steps 0 --no-configs --no-gpu-probe --write-latency-ms "$wl" \
         > "$out/burstcp_wl$wl.log" 2>&1 || { echo "burstcp failed rc=$?" | tee -a "$out/SUMMARY.txt"; exit 1; }
       python tools/critical_path.py "$out/burst_wl$wl.audit.jsonl" --name-prefix burst-r1 > "$out/burstcp_wl$wl.json" || exit 1
@@ -231,7 +231,7 @@ PY
       sfx="wl${wl}_t${trim}_$(date +%s)"; log="$out/burststall_$sfx.log"; smp="$out/stall_sampler_$sfx.txt"
       python tools/stall_sampler.py --ms ${STALL_MS:-20} --seconds 290 > "$smp" 2>&1 &
       spid=$!
-      ODH_CHILD_STDERR_DIR=$PWD/$out/children_$sfx ODH_STALL_WATCHDOG_MS=${STALL_MS:-20} ODH_APISERVER_TRIM_S=$trim timeout -k 10 300 python bench.py --steps 5 --warmup 2 \
+      ODH_CHILD_STDERR_DIR=$PWD/$out/children_$sfx ODH_STALL_WATCHDOG_MS=${STALL_MS:-20} ODH_APISERVER_TRIM_S=$trim timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 \
         --burst 8 --burst-rounds "$rounds" --resident 0 --storage-steps 0 --no-configs --no-gpu-probe \
         --write-latency-ms "$wl" > "$log" 2>&1
       rc=$?
