@@ -1,0 +1,80 @@
+// C ABI of libodh_gpu_probe.so: every exported function and the layout of the counter block.
+//
+// gpu_probe.hip and probe_cli.cpp define these functions and include this header first, so
+// a definition that disagrees with its declaration does not compile.  ops/gpu.py spells the
+// same signatures for ctypes and mirrors the slot constants; tests/test_probe_abi.py reads
+// this file as text and holds the two sides together (one declaration per statement, every
+// constant as NAME = integer, keeps that parse trivial).
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+// The counter block: ODH_NCOUNT × i32 on the device, read back in one copy.  Slots 0-19 mean
+// the same on every path.  From slot 20 on, the CLI (probe_cli.cpp) and the graph path
+// (odh_probe_graph_create) each have a layout of their own: they share slots 20-23 and are
+// never used on the same block.
+enum {
+  ODH_NCOUNT = 32,
+  ODH_N_XCD = 8,
+  ODH_SLOT_XCD_BLOCKS = 0,         // [ODH_N_XCD] workgroups that ran on each XCD
+  ODH_SLOT_ERR_XCD = 8,            // [ODH_N_XCD] GEMM mismatches per XCD that computed them
+  ODH_SLOT_GEMM_ERR = 16,          // u32: GEMM mismatches
+  ODH_SLOT_HBM_ERR = 18,           // u64: HBM sweep mismatches
+  ODH_SLOT_CLI_XGMI_ERR = 20,      // u64: mismatches on the xGMI link this device reads
+  ODH_SLOT_CLI_RCCL_ERR = 22,      // u64: mismatches in this device's RCCL all-reduce result
+  ODH_SLOT_GRAPH_GEMM_SPAN = 20,   // 2 × u64: ~(earliest begin), latest end (wall_clock64 ticks)
+  ODH_SLOT_GRAPH_SWEEP_SPAN = 24,  // 2 × u64: the same for the HBM write + check
+};
+static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
+static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
+static_assert(ODH_SLOT_GEMM_ERR + 1 <= ODH_SLOT_HBM_ERR && ODH_SLOT_HBM_ERR % 2 == 0, "HBM mismatches: aligned u64");
+static_assert(ODH_SLOT_HBM_ERR + 2 <= ODH_SLOT_CLI_XGMI_ERR && ODH_SLOT_CLI_XGMI_ERR % 2 == 0, "CLI layout");
+static_assert(ODH_SLOT_CLI_XGMI_ERR + 2 <= ODH_SLOT_CLI_RCCL_ERR && ODH_SLOT_CLI_RCCL_ERR + 2 <= ODH_NCOUNT,
+              "CLI layout exceeds the block");
+static_assert(ODH_SLOT_HBM_ERR + 2 <= ODH_SLOT_GRAPH_GEMM_SPAN && ODH_SLOT_GRAPH_GEMM_SPAN % 2 == 0, "graph layout");
+static_assert(ODH_SLOT_GRAPH_GEMM_SPAN + 4 <= ODH_SLOT_GRAPH_SWEEP_SPAN &&
+                  ODH_SLOT_GRAPH_SWEEP_SPAN + 4 <= ODH_NCOUNT,
+              "graph layout exceeds the block");
+
+extern "C" {
+
+// every function returning int returns a hipError_t (0 = success) unless noted
+int odh_gemm_shape_ok(int M, int N, int K);  // bool: multiples of the 128×128×32 tile
+int odh_gemm_tiles(int M, int N, int K);     // workgroups the GEMM launches (0: bad shape)
+const char* odh_error_string(int code);
+int odh_wall_clock_khz(int device);  // wall_clock64() tick rate (0 on error)
+int odh_probe_preload();
+int odh_probe_fill(void* A, void* Bt, int M, int N, int K, hipStream_t stream);
+int odh_gemm_bf16(const void* A, const void* Bt, float* C, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
+                  hipStream_t stream);
+int odh_gemm_bf16_128(const void* A, const void* Bt, float* C, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
+                      hipStream_t stream);
+int odh_gemm_bf16_256_variant(const void* A, const void* Bt, float* C, int M, int N, int K, int variant,
+                              hipStream_t stream);
+int odh_probe_verify(const float* C, int M, int N, int K, const int* tile_xcd, unsigned* err_total,
+                     unsigned* err_xcd, hipStream_t stream);
+int odh_probe_gemm_verify(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
+                          unsigned* err_total, unsigned* err_xcd, hipStream_t stream);
+int odh_probe_gemm_verify_2buf(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
+                               unsigned* err_total, unsigned* err_xcd, hipStream_t stream);
+int odh_probe_gemm_verify_deep(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
+                               unsigned* err_total, unsigned* err_xcd, int variant, hipStream_t stream);
+int odh_hbm_write(void* buf, size_t bytes, uint32_t seed, int nontemporal, hipStream_t stream);
+int odh_hbm_write_variant(void* buf, size_t bytes, uint32_t seed, int variant, int blocks, hipStream_t stream);
+int odh_hbm_check(const void* buf, size_t bytes, uint32_t seed, unsigned long long* err, hipStream_t stream);
+int odh_hbm_check_variant(const void* buf, size_t bytes, uint32_t seed, unsigned long long* err, int variant,
+                          int blocks, hipStream_t stream);
+int odh_const_check(const void* buf, size_t bytes, uint32_t expect, unsigned long long* err, hipStream_t stream);
+int odh_peer_enable(int dev, int peer);
+int odh_busy(float* out, int blocks, int iters, hipStream_t stream);
+// counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
+int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
+                           void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);
+int odh_probe_graph_launch(void* handle, hipStream_t stream);
+void odh_probe_graph_destroy(void* handle);
+// the start-up probe program (probe_cli.cpp); returns the process exit status
+int odh_probe_cli(int argc, char** argv);
+
+}  // extern "C"

@@ -6,7 +6,8 @@
 // hand to a notebook is healthy before the pod is reported Ready, and drives synthetic
 // load for the GPU-busy culler.  Everything here is written for CDNA4 directly:
 //
-//  * odh_probe_gemm  — bf16 GEMM on the matrix cores (v_mfma_f32_32x32x16_bf16),
+//  * odh_gemm_bf16 — bf16 GEMM on the matrix cores (v_mfma_f32_32x32x16_bf16), fp32 out:
+//    the 256×256×64 LDS-DMA kernel where it divides the shape, else odh_gemm_bf16_128:
 //    128×128 tile per 256-thread workgroup (4 waves, 2×2 of 32×32 MFMA tiles each),
 //    K staged through LDS in 32-deep double-buffered tiles with an XOR swizzle that
 //    makes the 16-lane ds_read_b128 groups conflict-free, and an XCD-aware blockIdx
@@ -21,16 +22,23 @@
 //    second GEMM: every element is compared bit-exactly on the GPU.
 //  * odh_hbm_write / odh_hbm_check — 16 B/lane streaming pattern write + verify over a
 //    resident HBM3E buffer (bandwidth and bit errors in one pass).
-//  * odh_peer_enable — lets one GPU read another's HBM over xGMI; the node agent's
-//    multi-GPU probe then runs odh_hbm_check on GPU j against GPU i's freshly written
-//    pattern buffer (a ring over the pod's GPUs: every link verified, per-link GB/s).
+//  * odh_peer_enable — lets one GPU read another's HBM over xGMI; the multi-GPU probe
+//    then runs odh_hbm_check on GPU j against GPU i's freshly written pattern buffer (a
+//    ring over the pod's GPUs: every link verified, per-link GB/s).
+//  * odh_const_check — every word of a buffer equal to one value (the RCCL result check).
+//  * odh_probe_graph_create / _launch / _destroy — the probe captured as one hipGraph.
+//  * odh_gemm_bf16_256_variant, odh_probe_gemm_verify_2buf / _deep, odh_hbm_write_variant,
+//    odh_hbm_check_variant — A/B entry points (microbenchmarks, kernel numerics tests).
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
-// C ABI only (loaded with ctypes after torch, sharing torch's libamdhip64.so.7).
+// C ABI only, declared in gpu_probe.h (loaded with ctypes after torch, sharing torch's
+// libamdhip64.so.7; linked by odh-gpu-probe).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gpu_probe.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -194,6 +202,12 @@ __device__ int probe_expect(int ia5, int jb7, int K) {
   return s;
 }
 
+// bijective XCD remap: the blocks dispatched to one XCD (orig % 8) take consecutive tiles
+__device__ __forceinline__ int xcd_tile(int orig, int nwg) {
+  const int xq = nwg >> 3, xr = nwg & 7, xs = orig & 7;
+  return (xs < xr ? xs * (xq + 1) : xr * (xq + 1) + (xs - xr) * xq) + (orig >> 3);
+}
+
 template <bool VERIFY, bool PIPE = true>
 __global__ __launch_bounds__(G_THREADS, 1) void gemm256_kernel(
     const uint4* __restrict__ A, const uint4* __restrict__ Bt, float* __restrict__ C, int /*M*/, int N, int K,
@@ -207,10 +221,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256_kernel(
   const int w = tid >> 6;
   const int wm = w >> 2, wn = w & 3;
   const int tiles_n = N / G_BN;
-  const int nwg = gridDim.x;
-  // bijective XCD remap: the blocks dispatched to one XCD (orig % 8) take consecutive tiles
-  const int orig = blockIdx.x, xq = nwg >> 3, xr = nwg & 7, xs = orig & 7;
-  const int bid = (xs < xr ? xs * (xq + 1) : xr * (xq + 1) + (xs - xr) * xq) + (orig >> 3);
+  const int bid = xcd_tile(blockIdx.x, gridDim.x);
   const int tm = bid / tiles_n;
   const int tn = bid - tm * tiles_n;
   const unsigned xcc = xcc_id();
@@ -323,7 +334,13 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256_kernel(
   }
 }
 
-bool gemm256_ok(int M, int N, int K) { return M % G_BM == 0 && N % G_BN == 0 && K % G_BK == 0; }
+// host side: shapes the 256² kernels take (every one of them passes odh_gemm_shape_ok), their
+// workgroup count, and the guard of the fused probe entry points
+bool gemm256_ok(int M, int N, int K) {
+  return M > 0 && N > 0 && K > 0 && M % G_BM == 0 && N % G_BN == 0 && K % G_BK == 0;
+}
+int gemm256_tiles(int M, int N) { return (M / G_BM) * (N / G_BN); }
+bool fused_probe_ok(int M, int N, int K, const unsigned* err_total) { return gemm256_ok(M, N, K) && err_total; }
 
 // ---------------------------------------------------------------------------------------
 // Deep-pipelined 256×256 tile: BK = 32 stages in a 4-buffer LDS ring (4 × 32 KiB), with
@@ -370,9 +387,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
   const int w = tid >> 6;
   const int wm = w >> 2, wn = w & 3;
   const int tiles_n = N / G_BN;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x, xq = nwg >> 3, xr = nwg & 7, xs = orig & 7;
-  const int bid = (xs < xr ? xs * (xq + 1) : xr * (xq + 1) + (xs - xr) * xq) + (orig >> 3);
+  const int bid = xcd_tile(blockIdx.x, gridDim.x);
   // GM > 1: consecutive tile ids walk GM tile-rows × (32/GM) columns, so the 32 tiles of
   // one XCD share GM A panels and 32/GM B panels in that XCD's L2 (GM = 1: row-major)
   int tm, tn;
@@ -525,6 +540,8 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
     }
   }
 
+  // the epilogue of gemm256_kernel, word for word: as a shared helper it compiles to other
+  // instructions in the VERIFY kernels, so both keep their copy
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -587,6 +604,8 @@ __global__ void verify_kernel(const float* __restrict__ C, int M, int N, int K, 
     bool bad = false;
     if (idx < total) {
       const int i = (int)(idx / N), j = (int)(idx - (size_t)i * N);
+      // probe_expect(i % 5, j % 7, K) with q and rem hoisted and the loop unrolled (a call
+      // to it compiles to other instructions here)
       const int ia = (i % 5) * 3 % 5, jb = (j % 7) * 11 % 7;
       int s = 0;
 #pragma unroll
@@ -614,6 +633,27 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   return x;
 }
 
+// the 16 bytes of pattern element i
+__device__ __forceinline__ u32x4 pattern16(size_t i, uint32_t seed) {
+  const uint32_t b = (uint32_t)(i * 4) ^ seed;
+  u32x4 v;
+  v.x = mix32(b);
+  v.y = mix32(b + 1);
+  v.z = mix32(b + 2);
+  v.w = mix32(b + 3);
+  return v;
+}
+
+// this workgroup's slab [lo, hi) of n elements: equal slabs, a multiple of 1024 elements long
+struct Slab {
+  size_t lo, hi;
+};
+__device__ __forceinline__ Slab slab_of(size_t n) {
+  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) & ~(size_t)1023;
+  const size_t lo = blockIdx.x * per;
+  return {lo, lo + per < n ? lo + per : n};
+}
+
 // Pattern sweeps: each workgroup owns one contiguous slab of the buffer (measured on
 // MI355X, 1 GiB: 5.9 TB/s for slabs vs 4.1 TB/s for a grid-stride loop of the same
 // stores; sequential DRAM pages per CU), 4 × 16 B per lane per iteration so every wave
@@ -624,20 +664,13 @@ __global__ __launch_bounds__(256) void hbm_write_kernel(u32x4* __restrict__ buf,
                                                         unsigned long long* __restrict__ ts = nullptr) {
   if (seedp) seed = *seedp;  // graph replays: the seed lives on the device
   if (ts && threadIdx.x == 0 && blockIdx.x < TS_EDGE) ts_begin(ts);
-  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) & ~(size_t)1023;
-  const size_t lo = blockIdx.x * per;
-  const size_t hi = lo + per < n ? lo + per : n;
+  const auto [lo, hi] = slab_of(n);
   for (size_t base = lo + threadIdx.x; base < hi; base += 4 * 256) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const size_t i = base + u * 256;
       if (i < hi) {
-        const uint32_t b = (uint32_t)(i * 4) ^ seed;
-        u32x4 v;
-        v.x = mix32(b);
-        v.y = mix32(b + 1);
-        v.z = mix32(b + 2);
-        v.w = mix32(b + 3);
+        const u32x4 v = pattern16(i, seed);
         if (NT)
           __builtin_nontemporal_store(v, &buf[i]);
         else
@@ -661,12 +694,7 @@ __global__ __launch_bounds__(256) void hbm_write_variant_kernel(u32x4* __restric
       for (int u = 0; u < 4; ++u) {
         const size_t i = w * 256 + u * 64 + lane;
         if (i < n) {
-          const uint32_t b = (uint32_t)(i * 4) ^ seed;
-          u32x4 v;
-          v.x = mix32(b);
-          v.y = mix32(b + 1);
-          v.z = mix32(b + 2);
-          v.w = mix32(b + 3);
+          const u32x4 v = pattern16(i, seed);
           buf[i] = v;
         }
       }
@@ -675,12 +703,7 @@ __global__ __launch_bounds__(256) void hbm_write_variant_kernel(u32x4* __restric
     const size_t per = (n + gridDim.x - 1) / gridDim.x;
     const size_t lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
     for (size_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-      const uint32_t b = (uint32_t)(i * 4) ^ seed;
-      u32x4 v;
-      v.x = mix32(b);
-      v.y = mix32(b + 1);
-      v.z = mix32(b + 2);
-      v.w = mix32(b + 3);
+      const u32x4 v = pattern16(i, seed);
       buf[i] = v;
     }
   } else {
@@ -696,9 +719,7 @@ __global__ __launch_bounds__(256) void hbm_check_kernel(const u32x4* __restrict_
                                                         const uint32_t* __restrict__ seedp = nullptr,
                                                         unsigned long long* __restrict__ ts = nullptr) {
   if (seedp) seed = *seedp;
-  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) & ~(size_t)1023;
-  const size_t lo = blockIdx.x * per;
-  const size_t hi = lo + per < n ? lo + per : n;
+  const auto [lo, hi] = slab_of(n);
   unsigned local = 0;
   for (size_t base = lo + threadIdx.x; base < hi; base += 4 * 256) {
     u32x4 v[4];
@@ -728,9 +749,7 @@ __global__ __launch_bounds__(256) void hbm_check_kernel(const u32x4* __restrict_
 template <bool NT, int U>
 __global__ __launch_bounds__(256) void hbm_check_variant_kernel(const u32x4* __restrict__ buf, size_t n,
                                                                 uint32_t seed, unsigned long long* __restrict__ err) {
-  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) & ~(size_t)1023;
-  const size_t lo = blockIdx.x * per;
-  const size_t hi = lo + per < n ? lo + per : n;
+  const auto [lo, hi] = slab_of(n);
   unsigned local = 0;
   for (size_t base = lo + threadIdx.x; base < hi; base += U * 256) {
     u32x4 v[U];
@@ -756,9 +775,7 @@ __global__ __launch_bounds__(256) void hbm_check_variant_kernel(const u32x4* __r
 // every 32-bit word of buf equal to `expect` (the RCCL all-reduce result check)
 __global__ __launch_bounds__(256) void const_check_kernel(const u32x4* __restrict__ buf, size_t n, uint32_t expect,
                                                           unsigned long long* __restrict__ err) {
-  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) & ~(size_t)1023;
-  const size_t lo = blockIdx.x * per;
-  const size_t hi = lo + per < n ? lo + per : n;
+  const auto [lo, hi] = slab_of(n);
   unsigned local = 0;
   for (size_t i = lo + threadIdx.x; i < hi; i += 256) {
     const u32x4 v = __builtin_nontemporal_load(&buf[i]);
@@ -841,8 +858,8 @@ int odh_gemm_bf16_128(const void* A, const void* Bt, float* C, int M, int N, int
 // deep-pipelined BK=32 / 4-buffer ring (variant 2)
 int odh_gemm_bf16_256_variant(const void* A, const void* Bt, float* C, int M, int N, int K, int variant,
                               hipStream_t stream) {
-  if (!odh_gemm_shape_ok(M, N, K) || !gemm256_ok(M, N, K)) return (int)hipErrorInvalidValue;
-  const int nwg = (M / G_BM) * (N / G_BN);
+  if (!gemm256_ok(M, N, K)) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
   if (variant == 0)
     gemm256_kernel<false, false><<<nwg, G_THREADS, 0, stream>>>((const uint4*)A, (const uint4*)Bt, C, M, N, K,
                                                                  nullptr, nullptr, nullptr, nullptr);
@@ -861,14 +878,14 @@ int odh_gemm_bf16_256_variant(const void* A, const void* Bt, float* C, int M, in
 // workgroups (= tiles) the GEMM launches for this shape: 256² tiles when they fit, else 128²
 int odh_gemm_tiles(int M, int N, int K) {
   if (!odh_gemm_shape_ok(M, N, K)) return 0;
-  return gemm256_ok(M, N, K) ? (M / G_BM) * (N / G_BN) : (M / BM) * (N / BN);
+  return gemm256_ok(M, N, K) ? gemm256_tiles(M, N) : (M / BM) * (N / BN);
 }
 
 int odh_gemm_bf16(const void* A, const void* Bt, float* C, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
                   hipStream_t stream) {
   if (!odh_gemm_shape_ok(M, N, K)) return (int)hipErrorInvalidValue;
   if (gemm256_ok(M, N, K)) {
-    gemm256_kernel<false><<<(M / G_BM) * (N / G_BN), G_THREADS, 0, stream>>>(
+    gemm256_kernel<false><<<gemm256_tiles(M, N), G_THREADS, 0, stream>>>(
         (const uint4*)A, (const uint4*)Bt, C, M, N, K, tile_xcd, xcd_blocks, nullptr, nullptr);
     return (int)hipGetLastError();
   }
@@ -888,16 +905,16 @@ int odh_probe_verify(const float* C, int M, int N, int K, const int* tile_xcd, u
 // 2-buffer BK=64 kernel, which stays exported as odh_probe_gemm_verify_2buf for A/B).
 int odh_probe_gemm_verify(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
                           unsigned* err_total, unsigned* err_xcd, hipStream_t stream) {
-  if (!odh_gemm_shape_ok(M, N, K) || !gemm256_ok(M, N, K) || !err_total) return (int)hipErrorInvalidValue;
-  gemm256d_kernel<true><<<(M / G_BM) * (N / G_BN), G_THREADS, 0, stream>>>(
+  if (!fused_probe_ok(M, N, K, err_total)) return (int)hipErrorInvalidValue;
+  gemm256d_kernel<true><<<gemm256_tiles(M, N), G_THREADS, 0, stream>>>(
       (const uint4*)A, (const uint4*)Bt, nullptr, M, N, K, tile_xcd, xcd_blocks, err_total, err_xcd);
   return (int)hipGetLastError();
 }
 
 int odh_probe_gemm_verify_2buf(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
                                unsigned* err_total, unsigned* err_xcd, hipStream_t stream) {
-  if (!odh_gemm_shape_ok(M, N, K) || !gemm256_ok(M, N, K) || !err_total) return (int)hipErrorInvalidValue;
-  gemm256_kernel<true><<<(M / G_BM) * (N / G_BN), G_THREADS, 0, stream>>>(
+  if (!fused_probe_ok(M, N, K, err_total)) return (int)hipErrorInvalidValue;
+  gemm256_kernel<true><<<gemm256_tiles(M, N), G_THREADS, 0, stream>>>(
       (const uint4*)A, (const uint4*)Bt, nullptr, M, N, K, tile_xcd, xcd_blocks, err_total, err_xcd);
   return (int)hipGetLastError();
 }
@@ -906,8 +923,8 @@ int odh_probe_gemm_verify_2buf(const void* A, const void* Bt, int M, int N, int 
 // variant bit 0: cross-barrier fragment prefetch (XB); bits 1-2: tile grouping GM = 1, 2, 4, 8
 int odh_probe_gemm_verify_deep(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
                                unsigned* err_total, unsigned* err_xcd, int variant, hipStream_t stream) {
-  if (!odh_gemm_shape_ok(M, N, K) || !gemm256_ok(M, N, K) || !err_total) return (int)hipErrorInvalidValue;
-  const int nwg = (M / G_BM) * (N / G_BN);
+  if (!fused_probe_ok(M, N, K, err_total)) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
   const uint4 *a = (const uint4*)A, *b = (const uint4*)Bt;
 #define ODH_DEEP(XB_, GM_)                                                                                  \
   gemm256d_kernel<true, XB_, GM_><<<nwg, G_THREADS, 0, stream>>>(a, b, nullptr, M, N, K, tile_xcd, xcd_blocks, \
@@ -939,17 +956,18 @@ int odh_hbm_write(void* buf, size_t bytes, uint32_t seed, int nontemporal, hipSt
 
 // ------------------------------------------------------------------ the probe as one hipGraph
 //
-// The start-up probe is launch-bound on the host side: a counter reset, the GEMM on one
-// stream, the HBM write + check on a second, a fork/join and a 128-byte read-back — five
-// launches and three stream operations per pod start.  odh_probe_graph_create captures
+// For the torch-side harness (ops/gpu.py::GpuProbe; the shipped odh-gpu-probe launches
+// eagerly on the null stream).  A resident probe is launch-bound on the host side: a counter
+// reset, the GEMM on one stream, the HBM write + check on a second, a fork/join and a 128-byte
+// read-back — five launches and three stream operations per run.  odh_probe_graph_create captures
 // them once (stream capture with an event fork/join, so the sweep and the GEMM still run
 // concurrently) and odh_probe_graph_launch replays the whole probe with one launch.  A
 // graph freezes kernel arguments, so the per-run HBM pattern seed lives on the device: the
 // first node advances it (LCG) and the sweep kernels read it.
 
-// first node: advance the seed and reset the 32 counters (one wave; no memset node)
+// first node: advance the seed and reset the counter block (one wave; no memset node)
 __global__ void probe_seed_advance_kernel(uint32_t* seed, int* counters) {
-  if (threadIdx.x < 32) counters[threadIdx.x] = 0;
+  if (threadIdx.x < ODH_NCOUNT) counters[threadIdx.x] = 0;
   if (threadIdx.x == 0) *seed = *seed * 1664525u + 1013904223u;
 }
 
@@ -972,12 +990,11 @@ static void probe_graph_free(ProbeGraph* g) {
   delete g;
 }
 
-// counters: 32 × i32 on the device ([0:8] xcd_blocks, [8:16] err_xcd, [16] gemm errors, [18:20]
-// hbm errors as u64, [20:24] GEMM span, [24:28] sweep span as ts_begin/ts_end u64 pairs);
-// host: 32 × i32 pinned; seed: one u32 on the device
+// counters: the counter block on the device in the graph layout of gpu_probe.h (the spans are
+// ts_begin / ts_end pairs); host: the same size, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out) {
-  if (!out || !odh_gemm_shape_ok(M, N, K) || !gemm256_ok(M, N, K) || hbm_bytes < 16) return (int)hipErrorInvalidValue;
+  if (!out || !gemm256_ok(M, N, K) || hbm_bytes < 16) return (int)hipErrorInvalidValue;
   *out = nullptr;
   ProbeGraph* g = new ProbeGraph();
   hipError_t e = hipStreamCreateWithFlags(&g->s0, hipStreamNonBlocking);
@@ -1006,20 +1023,22 @@ int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, i
   }
   // the memory-bound sweep on the second stream, issued first; the GEMM's one workgroup
   // per CU co-resides with its waves
-  unsigned long long* ts = (unsigned long long*)(counters + 20);
-  hbm_write_kernel<false><<<grid_for(n, 1024), 256, 0, sw>>>((u32x4*)hbm, n, 0u, seed, ts + 2);
+  unsigned long long* gemm_span = (unsigned long long*)(counters + ODH_SLOT_GRAPH_GEMM_SPAN);
+  unsigned long long* sweep_span = (unsigned long long*)(counters + ODH_SLOT_GRAPH_SWEEP_SPAN);
+  hbm_write_kernel<false><<<grid_for(n, 1024), 256, 0, sw>>>((u32x4*)hbm, n, 0u, seed, sweep_span);
   chk(hipGetLastError());
-  hbm_check_kernel<<<grid_for(n, 1024), 256, 0, sw>>>((const u32x4*)hbm, n, 0u,
-                                                           (unsigned long long*)(counters + 18), seed, ts + 2);
+  hbm_check_kernel<<<grid_for(n, 1024), 256, 0, sw>>>(
+      (const u32x4*)hbm, n, 0u, (unsigned long long*)(counters + ODH_SLOT_HBM_ERR), seed, sweep_span);
   chk(hipGetLastError());
-  gemm256d_kernel<true><<<(M / G_BM) * (N / G_BN), G_THREADS, 0, g->s0>>>(
-      (const uint4*)A, (const uint4*)Bt, nullptr, M, N, K, tile_xcd, counters, c + 16, c + 8, ts);
+  gemm256d_kernel<true><<<gemm256_tiles(M, N), G_THREADS, 0, g->s0>>>(
+      (const uint4*)A, (const uint4*)Bt, nullptr, M, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+      c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD, gemm_span);
   chk(hipGetLastError());
   if (!serial) {
     chk(hipEventRecord(g->join, g->s1));
     chk(hipStreamWaitEvent(g->s0, g->join, 0));
   }
-  chk(hipMemcpyAsync(host, counters, 32 * sizeof(int), hipMemcpyDeviceToHost, g->s0));
+  chk(hipMemcpyAsync(host, counters, ODH_NCOUNT * sizeof(int), hipMemcpyDeviceToHost, g->s0));
   e = hipStreamEndCapture(g->s0, &g->graph);
   if (e == hipSuccess && cap != hipSuccess) e = cap;
   if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);

@@ -9,8 +9,9 @@
 //      integer-valued bf16 operands on the GPU (odh_probe_fill);
 //   2. runs the MFMA bf16 GEMM with the check fused into its epilogue
 //      (odh_probe_gemm_verify: every output element compared in registers against a closed
-//      form, mismatches attributed to the XCD that computed them) concurrently with the
-//      HBM pattern write + verify sweep on a second stream;
+//      form, mismatches attributed to the XCD that computed them), then the HBM pattern
+//      write + verify sweep, both on the device's null stream (--streams 0, the default;
+//      --streams 2 overlaps the sweep with the GEMM on a second stream);
 //   3. with 2+ GPUs, reads every link of a ring over them through xGMI (peer access) and
 //      verifies the neighbour's pattern word for word;
 //   4. with --rccl-mib N (the `amd.com/gpu-probe: "rccl"` notebooks), an RCCL all-reduce over
@@ -45,18 +46,7 @@
 #include <unistd.h>
 #include <vector>
 
-extern "C" {
-int odh_gemm_shape_ok(int M, int N, int K);
-int odh_gemm_tiles(int M, int N, int K);
-int odh_probe_fill(void* A, void* Bt, int M, int N, int K, hipStream_t stream);
-int odh_probe_preload();
-int odh_probe_gemm_verify(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* xcd_blocks,
-                          unsigned* err_total, unsigned* err_xcd, hipStream_t stream);
-int odh_hbm_write(void* buf, size_t bytes, uint32_t seed, int nontemporal, hipStream_t stream);
-int odh_hbm_check(const void* buf, size_t bytes, uint32_t seed, unsigned long long* err, hipStream_t stream);
-int odh_peer_enable(int dev, int peer);
-int odh_const_check(const void* buf, size_t bytes, uint32_t expect, unsigned long long* err, hipStream_t stream);
-}
+#include "gpu_probe.h"
 
 namespace {
 
@@ -83,18 +73,14 @@ struct Options {
   int streams = 0;
 };
 
-// device counters: [0:8] workgroups per XCD, [8:16] mismatches per XCD, [16] GEMM mismatches,
-// [18:20] HBM mismatches (u64), [20:22] xGMI mismatches of the link this device reads (u64),
-// [22:24] mismatches in this device's RCCL all-reduce result (u64)
-constexpr int NCOUNT = 32;
-
+// device counters: the counter block of gpu_probe.h in its CLI layout
 struct Dev {
   int index = 0;
   void* block = nullptr;  // the one allocation every buffer below is carved from
   void *a = nullptr, *bt = nullptr, *hbm = nullptr;
   int* tile_xcd = nullptr;
   int* counters = nullptr;
-  int host[NCOUNT] = {};
+  int host[ODH_NCOUNT] = {};
   hipStream_t sg = nullptr, sh = nullptr;
   hipEvent_t e0 = nullptr, e_gemm = nullptr, e_h0 = nullptr, e_h1 = nullptr, e_link0 = nullptr, e_link1 = nullptr;
   hipEvent_t e_r0 = nullptr, e_r1 = nullptr;
@@ -213,7 +199,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t na = align_up((size_t)o.M * o.K * 2), nb = align_up((size_t)o.N * o.K * 2);
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + align_up(sizeof(int) * NCOUNT)));
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + align_up(sizeof(int) * ODH_NCOUNT)));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -233,7 +219,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   // the first operation on the stream: on the null stream it creates the hardware queue, here
   // while the other thread is still loading the code object
   t0 = Clock::now();
-  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * NCOUNT, d.sg));
+  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT, d.sg));
   d.first_op_ms = ms_since(t0);
   return true;
 }
@@ -256,7 +242,7 @@ bool launch(Dev& d, const Options& o) {
     HIP_TRY(hipEventRecord(d.e_h0, d.sh));
     HIP_TRY(odh_hbm_write(d.hbm, o.hbm_bytes, d.seed, 0, d.sh));
     HIP_TRY(odh_hbm_check(d.hbm, o.hbm_bytes, o.fault == "hbm" ? d.seed + 1 : d.seed,
-                          (unsigned long long*)(d.counters + 18), d.sh));
+                          (unsigned long long*)(d.counters + ODH_SLOT_HBM_ERR), d.sh));
     HIP_TRY(hipEventRecord(d.e_h1, d.sh));
     return true;
   };
@@ -267,7 +253,8 @@ bool launch(Dev& d, const Options& o) {
     HIP_TRY(hipStreamWaitEvent(d.sh, d.e0, 0));
     if (!sweep()) return false;
   }
-  HIP_TRY(odh_probe_gemm_verify(d.a, d.bt, o.M, o.N, o.K, d.tile_xcd, d.counters, c + 16, c + 8, d.sg));
+  HIP_TRY(odh_probe_gemm_verify(d.a, d.bt, o.M, o.N, o.K, d.tile_xcd, d.counters + ODH_SLOT_XCD_BLOCKS,
+                                c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD, d.sg));
   HIP_TRY(hipEventRecord(d.e_gemm, d.sg));
   // one stream: the sweep after the GEMM, so e0..e_gemm still times the GEMM alone
   if (d.sh == d.sg && !sweep()) return false;
@@ -294,8 +281,8 @@ bool link_check(Dev& d, const Dev& s, const Options& o) {
   HIP_TRY(hipSetDevice(d.index));
   const size_t n = (o.xgmi_bytes < o.hbm_bytes ? o.xgmi_bytes : o.hbm_bytes) & ~(size_t)15;
   HIP_TRY(hipEventRecord(d.e_link0, d.sg));
-  HIP_TRY(odh_hbm_check(s.hbm, n, o.fault == "xgmi" ? s.seed ^ 1u : s.seed, (unsigned long long*)(d.counters + 20),
-                        d.sg));
+  HIP_TRY(odh_hbm_check(s.hbm, n, o.fault == "xgmi" ? s.seed ^ 1u : s.seed,
+                        (unsigned long long*)(d.counters + ODH_SLOT_CLI_XGMI_ERR), d.sg));
   HIP_TRY(hipEventRecord(d.e_link1, d.sg));
   d.link_source = s.index;
   return true;
@@ -371,7 +358,7 @@ struct RcclRun {
 // Sum-all-reduce of float32 over every device: device i contributes i+1, so every element
 // of every result must be n(n+1)/2 (exact in float).  Send / receive buffers are the two
 // halves of each device's (already checked) HBM buffer.  On return each device's mismatch
-// count sits in its counters[22:24] and host[22:24].
+// count sits in slot ODH_SLOT_CLI_RCCL_ERR of its counters and of its host copy.
 bool rccl_allreduce(std::vector<Dev>& devs, const Options& o, RcclRun& run, std::string& err) {
   Rccl rc;
   const auto t_load = Clock::now();
@@ -403,7 +390,7 @@ bool rccl_allreduce(std::vector<Dev>& devs, const Options& o, RcclRun& run, std:
     hipError_t e = hipSetDevice(d.index);
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)d.hbm, (int)bits, count, d.sg);
     if (e == hipSuccess) e = hipMemsetAsync((char*)d.hbm + run.bytes, 0, run.bytes, d.sg);
-    if (e == hipSuccess) e = hipMemsetAsync(d.counters + 22, 0, 8, d.sg);
+    if (e == hipSuccess) e = hipMemsetAsync(d.counters + ODH_SLOT_CLI_RCCL_ERR, 0, 8, d.sg);
     if (e == hipSuccess) e = hipEventRecord(d.e_r0, d.sg);
     if (e != hipSuccess) return hip_fail(d, "fill", e);
   }
@@ -428,8 +415,10 @@ bool rccl_allreduce(std::vector<Dev>& devs, const Options& o, RcclRun& run, std:
     if (e == hipSuccess) e = hipEventRecord(d.e_r1, d.sg);
     if (e == hipSuccess)
       e = (hipError_t)odh_const_check((char*)d.hbm + run.bytes, run.bytes, want_bits,
-                                      (unsigned long long*)(d.counters + 22), d.sg);
-    if (e == hipSuccess) e = hipMemcpyAsync(d.host + 22, d.counters + 22, 8, hipMemcpyDeviceToHost, d.sg);
+                                      (unsigned long long*)(d.counters + ODH_SLOT_CLI_RCCL_ERR), d.sg);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(d.host + ODH_SLOT_CLI_RCCL_ERR, d.counters + ODH_SLOT_CLI_RCCL_ERR, 8, hipMemcpyDeviceToHost,
+                         d.sg);
     if (e != hipSuccess) return hip_fail(d, "check", e);
   }
   for (Dev& d : devs) {
@@ -564,11 +553,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     const int* h = d.host;
     long blocks = 0;
     int xcds = 0;
-    for (int x = 0; x < 8; ++x) {
-      blocks += h[x];
-      xcds += h[x] > 0;
+    for (int x = 0; x < ODH_N_XCD; ++x) {
+      blocks += h[ODH_SLOT_XCD_BLOCKS + x];
+      xcds += h[ODH_SLOT_XCD_BLOCKS + x] > 0;
     }
-    const uint64_t gemm_err = (uint32_t)h[16], hbm_err = u64(h, 18);
+    const uint64_t gemm_err = (uint32_t)h[ODH_SLOT_GEMM_ERR], hbm_err = u64(h, ODH_SLOT_HBM_ERR);
     const bool dok = gemm_err == 0 && hbm_err == 0 && blocks == tiles;
     if (!dok && first_err.empty()) {
       char b[160];
@@ -578,7 +567,8 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     }
     ok = ok && dok;
     std::string ex = "[";
-    for (int x = 0; x < 8; ++x) ex += std::to_string((unsigned)h[8 + x]) + (x < 7 ? "," : "]");
+    for (int x = 0; x < ODH_N_XCD; ++x)
+      ex += std::to_string((unsigned)h[ODH_SLOT_ERR_XCD + x]) + (x < ODH_N_XCD - 1 ? "," : "]");
     char b[512];
     std::snprintf(b, sizeof b,
                   "%s{\"device\":%d,\"ok\":%s,\"gemm_tflops\":%.1f,\"hbm_gbps\":%.1f,\"gemm_ms\":%.4f,\"hbm_ms\":%.4f,"
@@ -594,7 +584,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   if (ndev >= 2) {
     const size_t n = (o.xgmi_bytes < o.hbm_bytes ? o.xgmi_bytes : o.hbm_bytes) & ~(size_t)15;
     for (Dev& d : devs) {
-      const uint64_t lerr = u64(d.host, 20);
+      const uint64_t lerr = u64(d.host, ODH_SLOT_CLI_XGMI_ERR);
       const bool lok = lerr == 0;
       if (!lok && first_err.empty())
         first_err = "xGMI link GPU " + std::to_string(d.link_source) + " -> GPU " + std::to_string(d.index) + ": " +
@@ -613,7 +603,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     uint64_t rerr = 0;
     float slowest = 0;
     for (Dev& d : devs) {
-      rerr += u64(d.host, 22);
+      rerr += u64(d.host, ODH_SLOT_CLI_RCCL_ERR);
       slowest = d.rccl_ms > slowest ? d.rccl_ms : slowest;
     }
     const bool rok = rerr == 0;

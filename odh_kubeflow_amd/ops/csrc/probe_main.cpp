@@ -3,7 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" int odh_probe_cli(int argc, char** argv);
+#include "gpu_probe.h"
 
 int main(int argc, char** argv) {
   const int rc = odh_probe_cli(argc, argv);

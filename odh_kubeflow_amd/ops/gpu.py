@@ -1,27 +1,29 @@
 """Python side of the MI355X node-agent kernels (``csrc/gpu_probe.hip``).
 
 * :func:`gemm_bf16` — the MFMA bf16 GEMM (``C = A · Btᵀ``, fp32 out) on torch tensors.
-* :class:`GpuProbe` — the notebook start-up probe: a resident bf16 GEMM whose
-  integer-valued operands make every output element checkable bit-exactly on the GPU,
-  plus an HBM3E pattern write/verify sweep.  Sized as a health check on the create →
-  Ready path (:data:`PROBE_SHAPE`, :data:`PROBE_HBM_BYTES`): 4096×4096 outputs are 256
-  tiles of 256², one workgroup per CU of the 256-CU chip, so every CU of every XCD runs
-  MFMA work; K=1024 keeps the GEMM at ≈30 µs, and the 256 MiB sweep, interleaved over every
-  HBM3E stack and channel, tests them all (round 1 ran K=4096 and 1 GiB: ≈0.5 ms of GPU
-  time per pod start for the same coverage).  The probe is captured once into a hipGraph
-  (sweep and GEMM on two forked streams, counter reset, 128-byte read-back) and replayed
-  with ONE launch per pod start; the kernels time themselves (``wall_clock64`` spans), since
-  events cannot split a graph launch.  Reports matrix-core
-  TFLOP/s, HBM GB/s, mismatches (attributed to the XCD that computed them) and how many
-  of the 8 XCDs ran workgroups.
-* :func:`probe_devices` / :func:`xgmi_ring_check` — the same probe in a torch process over
-  several GPUs (kernel tests, microbenchmarks).  The shipped start-up probe is the
-  torch-free ``odh-gpu-probe`` init container (``csrc/probe_cli.cpp``, :mod:`.probe_main`),
-  which launches these same kernels from plain hipMalloc'd buffers.
+* :class:`GpuProbe` — the torch-side harness of the probe kernels, for kernel tests and
+  microbenchmarks: a resident bf16 GEMM whose integer-valued operands make every output
+  element checkable bit-exactly on the GPU, plus an HBM3E pattern write/verify sweep.  Sized
+  like the start-up probe (:data:`PROBE_SHAPE`, :data:`PROBE_HBM_BYTES`): 4096×4096 outputs
+  are 256 tiles of 256², one workgroup per CU of the 256-CU chip, so every CU of every XCD
+  runs MFMA work; K=1024 keeps the GEMM at ≈30 µs, and the 256 MiB sweep, interleaved over
+  every HBM3E stack and channel, tests them all.  It runs the kernels three ways: eager on
+  one stream, overlapped (sweep and GEMM on two streams), and as a hipGraph captured once
+  (forked streams, counter reset, 128-byte read-back) and replayed with one launch per
+  :meth:`GpuProbe.run`; in a graph the kernels time themselves (``wall_clock64`` spans),
+  since events cannot split a graph launch.  Reports matrix-core TFLOP/s, HBM GB/s,
+  mismatches (attributed to the XCD that computed them) and how many of the 8 XCDs ran
+  workgroups.
+* :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
+* The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
+  container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
+  from plain hipMalloc'd buffers, serially on the null stream.
 * :class:`LoadGenerator` — synthetic MFMA load at a given duty cycle (culler benchmarks).
 
-The library is loaded with ctypes **after** ``import torch`` so it binds to the HIP
-runtime torch already loaded.  If the ``.so`` is missing on a machine with a GPU the
+The library's C ABI is declared in ``csrc/gpu_probe.h``; :data:`SIGNATURES` and the ``ODH_*``
+counter slots below mirror it (``tests/test_probe_abi.py`` compares the two).  The library
+is loaded with ctypes **after** ``import torch`` so it binds to the HIP runtime torch already
+loaded.  If the ``.so`` is missing on a machine with a GPU the
 calls raise :class:`NativeLibraryMissing` instead of silently falling back.
 """
 
@@ -41,6 +43,57 @@ BK = 32
 N_XCD = 8
 PROBE_SHAPE = (4096, 4096, 1024)  # M, N, K of the start-up probe GEMM (256 tiles of 256²)
 PROBE_HBM_BYTES = 256 << 20
+
+# the counter block (csrc/gpu_probe.h): ODH_NCOUNT × i32; the CLI and graph layouts share
+# slots 20-23 and are never used on the same block
+ODH_NCOUNT = 32
+ODH_N_XCD = N_XCD
+ODH_SLOT_XCD_BLOCKS = 0  # [ODH_N_XCD] workgroups per XCD
+ODH_SLOT_ERR_XCD = 8  # [ODH_N_XCD] GEMM mismatches per XCD
+ODH_SLOT_GEMM_ERR = 16  # u32
+ODH_SLOT_HBM_ERR = 18  # u64
+ODH_SLOT_CLI_XGMI_ERR = 20  # u64 (odh-gpu-probe only)
+ODH_SLOT_CLI_RCCL_ERR = 22  # u64 (odh-gpu-probe only)
+ODH_SLOT_GRAPH_GEMM_SPAN = 20  # 2 × u64: ~begin, end (odh_probe_graph_create)
+ODH_SLOT_GRAPH_SWEEP_SPAN = 24  # 2 × u64
+
+_vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
+# name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
+SIGNATURES = {
+    "odh_gemm_shape_ok": (_i, [_i, _i, _i]),
+    "odh_gemm_tiles": (_i, [_i, _i, _i]),
+    "odh_error_string": (ctypes.c_char_p, [_i]),
+    "odh_wall_clock_khz": (_i, [_i]),
+    "odh_probe_fill": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "odh_gemm_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "odh_gemm_bf16_128": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "odh_probe_verify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "odh_probe_gemm_verify": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "odh_hbm_write": (_i, [_vp, _sz, _u32, _i, _vp]),
+    "odh_hbm_check": (_i, [_vp, _sz, _u32, _vp, _vp]),
+    "odh_peer_enable": (_i, [_i, _i]),
+    "odh_busy": (_i, [_vp, _i, _i, _vp]),
+    "odh_probe_graph_create": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "odh_probe_graph_launch": (_i, [_vp, _vp]),
+    "odh_probe_graph_destroy": (None, [_vp]),
+    # A/B entry points (microbenchmarks, kernel numerics tests)
+    "odh_gemm_bf16_256_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "odh_probe_gemm_verify_2buf": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "odh_probe_gemm_verify_deep": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "odh_hbm_write_variant": (_i, [_vp, _sz, _u32, _i, _i, _vp]),
+    "odh_hbm_check_variant": (_i, [_vp, _sz, _u32, _vp, _i, _i, _vp]),
+    # the start-up probe program (ops/probe_main.py)
+    "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
+}
+
+
+def bind(lib, names=SIGNATURES):
+    """Give the ctypes functions ``names`` of ``lib`` their :data:`SIGNATURES` (an export the
+    library lacks raises ``AttributeError`` here, not at its first call)."""
+    for name in names:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    return lib
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -73,40 +126,7 @@ def load_library(build_if_missing: bool = False):
                 build(verbose=False)
             if not os.path.exists(path):
                 raise NativeLibraryMissing(f"{path} not built; run `python -m odh_kubeflow_amd.ops.build`")
-        lib = ctypes.CDLL(path)
-        vp, i, u32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
-        lib.odh_gemm_shape_ok.argtypes = [i, i, i]
-        lib.odh_gemm_shape_ok.restype = i
-        lib.odh_error_string.argtypes = [i]
-        lib.odh_error_string.restype = ctypes.c_char_p
-        lib.odh_probe_fill.argtypes = [vp, vp, i, i, i, vp]
-        lib.odh_gemm_tiles.argtypes = [i, i, i]
-        lib.odh_gemm_tiles.restype = i
-        lib.odh_gemm_bf16.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
-        lib.odh_gemm_bf16_128.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
-        lib.odh_probe_verify.argtypes = [vp, i, i, i, vp, vp, vp, vp]
-        lib.odh_probe_gemm_verify.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp]
-        lib.odh_hbm_write.argtypes = [vp, sz, u32, i, vp]
-        lib.odh_hbm_check.argtypes = [vp, sz, u32, vp, vp]
-        lib.odh_busy.argtypes = [vp, i, i, vp]
-        lib.odh_peer_enable.argtypes = [i, i]
-        # A/B entry points (microbenchmarks, kernel numerics tests)
-        lib.odh_gemm_bf16_256_variant.argtypes = [vp, vp, vp, i, i, i, i, vp]
-        lib.odh_probe_gemm_verify_2buf.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp]
-        lib.odh_probe_gemm_verify_deep.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp]
-        lib.odh_hbm_write_variant.argtypes = [vp, sz, u32, i, i, vp]
-        lib.odh_hbm_check_variant.argtypes = [vp, sz, u32, vp, i, i, vp]
-        lib.odh_probe_graph_create.argtypes = [vp, vp, i, i, i, vp, vp, vp, sz, vp, vp, i, ctypes.POINTER(vp)]
-        lib.odh_probe_graph_launch.argtypes = [vp, vp]
-        lib.odh_probe_graph_destroy.argtypes = [vp]
-        lib.odh_probe_graph_destroy.restype = None
-        lib.odh_wall_clock_khz.argtypes = [i]
-        lib.odh_wall_clock_khz.restype = i
-        for f in ("odh_probe_fill", "odh_gemm_bf16", "odh_gemm_bf16_128", "odh_probe_verify", "odh_probe_gemm_verify",
-                  "odh_hbm_write", "odh_hbm_check", "odh_busy", "odh_gemm_bf16_256_variant",
-                  "odh_probe_gemm_verify_2buf", "odh_probe_gemm_verify_deep", "odh_hbm_write_variant",
-                  "odh_hbm_check_variant", "odh_peer_enable", "odh_probe_graph_create", "odh_probe_graph_launch"):
-            getattr(lib, f).restype = i
+        lib = bind(ctypes.CDLL(path))
         _lib = lib
         return lib
 
@@ -115,6 +135,11 @@ def _check(rc: int) -> None:
     if rc != 0:
         msg = load_library().odh_error_string(rc)
         raise HipError(f"HIP error {rc}: {msg.decode() if msg else '?'}")
+
+
+def _u64(h: Sequence[int], i: int) -> int:
+    """The u64 counter in i32 slots ``i`` and ``i + 1``."""
+    return (h[i] & 0xFFFFFFFF) | ((h[i + 1] & 0xFFFFFFFF) << 32)
 
 
 def _stream_ptr(device) -> int:
@@ -198,16 +223,16 @@ class GpuProbe:
             self.tiles = lib.odh_gemm_tiles(m, n, k)
             self.tile_xcd = torch.full(((m // BM) * (n // BN),), -1, dtype=torch.int32, device=self.device)
             self.hbm = torch.empty((hbm_bytes // 4,), dtype=torch.int32, device=self.device)
-            # counters: [0:8] xcd_blocks, [8:16] err_xcd, [16] gemm err, [18:20] hbm err (u64)
-            self.counters = torch.zeros((32,), dtype=torch.int32, device=self.device)
-            self.host = torch.zeros((32,), dtype=torch.int32).pin_memory()
+            # the counter block (ODH_SLOT_*; the graph path adds its spans)
+            self.counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=self.device)
+            self.host = torch.zeros((ODH_NCOUNT,), dtype=torch.int32).pin_memory()
             self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             self.streams = (torch.cuda.Stream(self.device), torch.cuda.Stream(self.device))
             _check(lib.odh_probe_fill(self.a.data_ptr(), self.bt.data_ptr(), m, n, k, _stream_ptr(self.device)))
             torch.cuda.current_stream(self.device).synchronize()
         self.hbm_nontemporal = hbm_nontemporal
         self.overlap = overlap
-        # graph replay: fused + overlapped probes (the start-up probe) — one launch per run
+        # graph replay: fused + overlapped probes — one launch per run
         self.graph = graph
         self._graph = None
         self._graph_error: Optional[str] = None
@@ -261,8 +286,8 @@ class GpuProbe:
                 self._graph = None
 
     def _span_ms(self, h: List[int], i: int) -> float:
-        begin = ~((h[i] & 0xFFFFFFFF) | ((h[i + 1] & 0xFFFFFFFF) << 32)) & 0xFFFFFFFFFFFFFFFF
-        end = (h[i + 2] & 0xFFFFFFFF) | ((h[i + 3] & 0xFFFFFFFF) << 32)
+        begin = ~_u64(h, i) & 0xFFFFFFFFFFFFFFFF
+        end = _u64(h, i + 2)
         return max(0.0, (end - begin) / self._tick_khz) if end and begin != 0xFFFFFFFFFFFFFFFF else 0.0
 
     def _launch_graph(self, graph) -> None:
@@ -277,8 +302,8 @@ class GpuProbe:
 
     def _graph_result(self, t0: float) -> dict:
         h = self.host.tolist()
-        return self._result(h, self._span_ms(h, 20), self._span_ms(h, 24), self.ev[0].elapsed_time(self.ev[4]), t0,
-                            graph=True)
+        return self._result(h, self._span_ms(h, ODH_SLOT_GRAPH_GEMM_SPAN), self._span_ms(h, ODH_SLOT_GRAPH_SWEEP_SPAN),
+                            self.ev[0].elapsed_time(self.ev[4]), t0, graph=True)
 
     def _run_graph(self, graph) -> dict:
         t0 = time.perf_counter()
@@ -294,7 +319,8 @@ class GpuProbe:
         with torch.cuda.device(self.device):
             sg, sh = self.streams
             cnt = self.counters
-            base = cnt.data_ptr()
+            xcd_blocks, err_xcd, gemm_err, hbm_err = (cnt.data_ptr() + 4 * slot for slot in (
+                ODH_SLOT_XCD_BLOCKS, ODH_SLOT_ERR_XCD, ODH_SLOT_GEMM_ERR, ODH_SLOT_HBM_ERR))
             self.seed = (self.seed * 1664525 + 1013904223) & 0xFFFFFFFF
             sg.wait_stream(torch.cuda.current_stream(self.device))  # caller's writes to a / bt / hbm
             with torch.cuda.stream(sg):
@@ -309,21 +335,21 @@ class GpuProbe:
                 self.ev[2].record(hs)
                 _check(lib.odh_hbm_write(self.hbm.data_ptr(), self.hbm_bytes, self.seed, int(self.hbm_nontemporal),
                                          h_))
-                _check(lib.odh_hbm_check(self.hbm.data_ptr(), self.hbm_bytes, self.seed, base + 18 * 4, h_))
+                _check(lib.odh_hbm_check(self.hbm.data_ptr(), self.hbm_bytes, self.seed, hbm_err, h_))
                 self.ev[3].record(hs)
 
             if self.overlap:
                 sweep()  # the longer, memory-bound part first: both are in flight together
             if self.fused:
                 _check(lib.odh_probe_gemm_verify(self.a.data_ptr(), self.bt.data_ptr(), self.m, self.n, self.k,
-                                                 self.tile_xcd.data_ptr(), base, base + 16 * 4, base + 8 * 4, g))
+                                                 self.tile_xcd.data_ptr(), xcd_blocks, gemm_err, err_xcd, g))
                 self.ev[1].record(sg)
             else:
                 _check(lib.odh_gemm_bf16(self.a.data_ptr(), self.bt.data_ptr(), self.c.data_ptr(), self.m, self.n,
-                                         self.k, self.tile_xcd.data_ptr(), base, g))
+                                         self.k, self.tile_xcd.data_ptr(), xcd_blocks, g))
                 self.ev[1].record(sg)
                 _check(lib.odh_probe_verify(self.c.data_ptr(), self.m, self.n, self.k, self.tile_xcd.data_ptr(),
-                                            base + 16 * 4, base + 8 * 4, g))
+                                            gemm_err, err_xcd, g))
             if not self.overlap:
                 sweep()
             else:
@@ -337,10 +363,10 @@ class GpuProbe:
                             self.ev[0].elapsed_time(self.ev[4]), t0, graph=False)
 
     def _result(self, h: List[int], gemm_ms: float, hbm_ms: float, probe_ms: float, t0: float, graph: bool) -> dict:
-        xcd_blocks = h[0:8]
-        err_xcd = h[8:16]
-        gemm_err = h[16] & 0xFFFFFFFF
-        hbm_err = (h[18] & 0xFFFFFFFF) | ((h[19] & 0xFFFFFFFF) << 32)
+        xcd_blocks = h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD]
+        err_xcd = h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]
+        gemm_err = h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF
+        hbm_err = _u64(h, ODH_SLOT_HBM_ERR)
         flops = 2.0 * self.m * self.n * self.k
         self.runs += 1
         ok = gemm_err == 0 and hbm_err == 0 and sum(xcd_blocks) == self.tiles
@@ -415,7 +441,7 @@ def xgmi_ring_check(devices: Sequence[int], nbytes: int = XGMI_CHECK_BYTES) -> L
                     ev1.synchronize()
                     e = err.cpu().tolist()
                 ms = ev0.elapsed_time(ev1)
-            errors = (e[0] & 0xFFFFFFFF) | ((e[1] & 0xFFFFFFFF) << 32)
+            errors = _u64(e, 0)
             r.update(ok=errors == 0, errors=errors, bytes=n, ms=ms, gbps=n / (ms * 1e-3) / 1e9 if ms > 0 else 0.0)
         except Exception as ex:  # a link that cannot be checked fails the pod, not the agent
             r["error"] = repr(ex)

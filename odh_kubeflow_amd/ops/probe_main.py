@@ -21,6 +21,7 @@ import sys
 from typing import List, Optional, Sequence
 
 from .build import PROBE_EXE, lib_path
+from .gpu import bind  # importing .gpu does not import torch
 
 PROBE_LIB = "libodh_gpu_probe.so"
 # exit statuses of odh_probe_cli
@@ -57,9 +58,7 @@ def run(argv: Sequence[str]) -> int:
     if not os.path.exists(path):
         sys.stderr.write(f"{path} not built; run `python -m odh_kubeflow_amd.ops.build`\n")
         return NO_GPU
-    lib = ctypes.CDLL(path)
-    lib.odh_probe_cli.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)]
-    lib.odh_probe_cli.restype = ctypes.c_int
+    lib = bind(ctypes.CDLL(path), ("odh_probe_cli",))
     args = ["odh-gpu-probe", *argv]
     arr = (ctypes.c_char_p * (len(args) + 1))(*[a.encode() for a in args], None)
     sys.stdout.flush()

@@ -131,18 +131,20 @@ def test_probe_verify_detects_corruption(dev):
     p.counters.zero_()
     p.c[5, 7] += 1.0
     p.c[700, 900] = float("nan")
+    cnt = p.counters.data_ptr()
     gpu._check(lib.odh_probe_verify(p.c.data_ptr(), p.m, p.n, p.k, p.tile_xcd.data_ptr(),
-                                    p.counters.data_ptr() + 64, p.counters.data_ptr() + 32, s))
+                                    cnt + 4 * gpu.ODH_SLOT_GEMM_ERR, cnt + 4 * gpu.ODH_SLOT_ERR_XCD, s))
     torch.cuda.synchronize()
     h = p.counters.cpu().tolist()
-    assert h[16] == 2 and sum(h[8:16]) == 2
+    assert h[gpu.ODH_SLOT_GEMM_ERR] == 2
+    assert sum(h[gpu.ODH_SLOT_ERR_XCD:gpu.ODH_SLOT_ERR_XCD + gpu.ODH_N_XCD]) == 2
     # HBM: flip one word after the pattern write
     p.counters.zero_()
     gpu._check(lib.odh_hbm_write(p.hbm.data_ptr(), p.hbm_bytes, 1234, 0, s))
     p.hbm[12345] ^= 1
-    gpu._check(lib.odh_hbm_check(p.hbm.data_ptr(), p.hbm_bytes, 1234, p.counters.data_ptr() + 72, s))
+    gpu._check(lib.odh_hbm_check(p.hbm.data_ptr(), p.hbm_bytes, 1234, cnt + 4 * gpu.ODH_SLOT_HBM_ERR, s))
     torch.cuda.synchronize()
-    assert p.counters.cpu().tolist()[18] == 1
+    assert p.counters.cpu().tolist()[gpu.ODH_SLOT_HBM_ERR] == 1
 
 
 def test_load_generator_runs(dev):
@@ -188,10 +190,12 @@ def test_deep_fused_probe_verify_counts_errors(dev, xb):
         p.counters.zero_()
         cnt = p.counters.data_ptr()
         gpu._check(lib.odh_probe_gemm_verify_deep(p.a.data_ptr(), p.bt.data_ptr(), p.m, p.n, p.k,
-                                                  p.tile_xcd.data_ptr(), cnt, cnt + 64, cnt + 32, xb, s))
+                                                  p.tile_xcd.data_ptr(), cnt + 4 * gpu.ODH_SLOT_XCD_BLOCKS,
+                                                  cnt + 4 * gpu.ODH_SLOT_GEMM_ERR, cnt + 4 * gpu.ODH_SLOT_ERR_XCD, xb, s))
         torch.cuda.synchronize()
         h = p.counters.cpu().tolist()
-        return h[16], sum(h[8:16]), sum(h[0:8])
+        return (h[gpu.ODH_SLOT_GEMM_ERR], sum(h[gpu.ODH_SLOT_ERR_XCD:gpu.ODH_SLOT_ERR_XCD + gpu.ODH_N_XCD]),
+                sum(h[gpu.ODH_SLOT_XCD_BLOCKS:gpu.ODH_SLOT_XCD_BLOCKS + gpu.ODH_N_XCD]))
 
     assert run_deep() == (0, 0, 16)
     expect_bad = int((p.bt[:, 7].float() != 0).sum().item())

@@ -46,9 +46,6 @@ def main():
         bt = (torch.rand((n, n), generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
         c = torch.empty((n, n), dtype=torch.float32, device=dev)
         fl = 2.0 * n ** 3
-        import ctypes
-
-        lib.odh_gemm_bf16_256_variant.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
         st = torch.cuda.current_stream().cuda_stream
         ref = a.float() @ bt.float().t()
         for v in (0, 1, 2, 3):  # 2-buffer BK=64 (v0 / v1 fragment-pipelined) vs deep BK=32 4-buffer ring (v2, v3 cross-barrier prefetch)
@@ -66,33 +63,29 @@ def main():
         out[f"gemm256_{n}_maxerr"] = float((c - ref).abs().max().item())
         del a, bt, c, ref
         torch.cuda.empty_cache()
-    import ctypes
-
     p = gpu.GpuProbe(0, 4096, 4096, 4096, hbm_bytes=1 << 30)  # the round-1 probe size: kernel A/B numbers
     s = torch.cuda.current_stream().cuda_stream
     cnt = p.counters.data_ptr()
+    xcd_blocks, gemm_err, err_xcd, hbm_err = (cnt + 4 * slot for slot in (
+        gpu.ODH_SLOT_XCD_BLOCKS, gpu.ODH_SLOT_GEMM_ERR, gpu.ODH_SLOT_ERR_XCD, gpu.ODH_SLOT_HBM_ERR))
     ms = timeit(lambda: lib.odh_probe_gemm_verify(p.a.data_ptr(), p.bt.data_ptr(), p.m, p.n, p.k,
-                                                  p.tile_xcd.data_ptr(), cnt, cnt + 64, cnt + 32, s))
+                                                  p.tile_xcd.data_ptr(), xcd_blocks, gemm_err, err_xcd, s))
     out["probe_gemm_fused_verify_4096"] = {"ms": round(ms, 4), "tflops": round(2.0 * 4096 ** 3 / ms / 1e9, 1)}
     ms = timeit(lambda: lib.odh_probe_gemm_verify_2buf(p.a.data_ptr(), p.bt.data_ptr(), p.m, p.n, p.k,
-                                                       p.tile_xcd.data_ptr(), cnt, cnt + 64, cnt + 32, s))
+                                                       p.tile_xcd.data_ptr(), xcd_blocks, gemm_err, err_xcd, s))
     out["probe_gemm_fused_verify_2buf_4096"] = {"ms": round(ms, 4), "tflops": round(2.0 * 4096 ** 3 / ms / 1e9, 1)}
     for rep in range(1):
         for v in range(8):  # bit 0 XB, bits 1-2 tile grouping GM = 1/2/4/8
             p.counters.zero_()
             ms = timeit(lambda: lib.odh_probe_gemm_verify_deep(p.a.data_ptr(), p.bt.data_ptr(), p.m, p.n, p.k,
-                                                               p.tile_xcd.data_ptr(), cnt, cnt + 64, cnt + 32, v, s))
+                                                               p.tile_xcd.data_ptr(), xcd_blocks, gemm_err, err_xcd, v, s))
             torch.cuda.synchronize()
             out[f"probe_gemm_fused_verify_deep_v{v}_r{rep}_4096"] = {
                 "ms": round(ms, 4), "tflops": round(2.0 * 4096 ** 3 / ms / 1e9, 1),
-                "errors": int(p.counters[16].item())}
+                "errors": int(p.counters[gpu.ODH_SLOT_GEMM_ERR].item())}
     for nt in (0, 1):
         ms = timeit(lambda: lib.odh_hbm_write(p.hbm.data_ptr(), p.hbm_bytes, 7, nt, s))
         out[f"hbm_write_nt{nt}_1GiB"] = {"ms": round(ms, 4), "gbps": round(p.hbm_bytes / ms / 1e6, 1)}
-    import ctypes
-
-    lib.odh_hbm_write_variant.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_void_p]
     for v in (1, 2, 3):
         for blocks in (1024, 2048, 4096, 8192):
             ms = timeit(lambda: lib.odh_hbm_write_variant(p.hbm.data_ptr(), p.hbm_bytes, 7, v, blocks, s))
@@ -105,16 +98,16 @@ def main():
     out["torch_fill_4GiB"] = {"ms": round(ms, 4), "gbps": round((4 << 30) / ms / 1e6, 1)}
     del big
     lib.odh_hbm_write(p.hbm.data_ptr(), p.hbm_bytes, 7, 0, s)  # check against a matching pattern (the probe's case)
-    ms = timeit(lambda: lib.odh_hbm_check(p.hbm.data_ptr(), p.hbm_bytes, 7, cnt + 72, s))
+    ms = timeit(lambda: lib.odh_hbm_check(p.hbm.data_ptr(), p.hbm_bytes, 7, hbm_err, s))
     out["hbm_check_1GiB"] = {"ms": round(ms, 4), "gbps": round(p.hbm_bytes / ms / 1e6, 1)}
     lib.odh_hbm_write(p.hbm.data_ptr(), p.hbm_bytes, 7, 0, s)
     for v in (0, 1, 2, 3):
         for blocks in (1024, 2048, 4096, 8192):
             p.counters.zero_()
-            ms = timeit(lambda: lib.odh_hbm_check_variant(p.hbm.data_ptr(), p.hbm_bytes, 7, cnt + 72, v, blocks, s))
+            ms = timeit(lambda: lib.odh_hbm_check_variant(p.hbm.data_ptr(), p.hbm_bytes, 7, hbm_err, v, blocks, s))
             torch.cuda.synchronize()
             out[f"hbm_check_v{v}_b{blocks}"] = {"ms": round(ms, 4), "gbps": round(p.hbm_bytes / ms / 1e6, 1),
-                                                "errors": int(p.counters[18].item())}
+                                                "errors": int(p.counters[gpu.ODH_SLOT_HBM_ERR].item())}
     ms = timeit(lambda: p.hbm.sum())
     out["torch_sum_1GiB"] = {"ms": round(ms, 4), "gbps": round(p.hbm_bytes / ms / 1e6, 1)}
     for ov in (False, True):
