@@ -136,8 +136,10 @@ bool parse(int argc, char** argv, Options& o) {
     }
   }
   // the fused check needs 256² output tiles and K in 64-element steps
+  // the probe operands sum to zero over their period of 35 in k: at K % 35 == 0 the expected
+  // product is 0 everywhere and matrix cores that return zeros would pass, so K is refused
   // the all-reduce's send and receive buffers are the two halves of the HBM buffer
-  return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 &&
+  return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 && o.K % 35 != 0 &&
          o.hbm_bytes >= (1u << 20) && o.timeout_ms > 0 && 2 * o.rccl_bytes <= o.hbm_bytes &&
          (o.fault != "rccl" || o.rccl_bytes > 0);
 }

@@ -71,6 +71,7 @@ SIGNATURES = {
     "odh_probe_gemm_verify": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "odh_hbm_write": (_i, [_vp, _sz, _u32, _i, _vp]),
     "odh_hbm_check": (_i, [_vp, _sz, _u32, _vp, _vp]),
+    "odh_const_check": (_i, [_vp, _sz, _u32, _vp, _vp]),
     "odh_peer_enable": (_i, [_i, _i]),
     "odh_busy": (_i, [_vp, _i, _i, _vp]),
     "odh_probe_graph_create": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(_vp)]),
@@ -161,6 +162,14 @@ def fused_verify_ok(m: int, n: int, k: int) -> bool:
     return gemm_shape_ok(m, n, k) and m % 256 == 0 and n % 256 == 0 and k % 64 == 0
 
 
+def probe_check_vacuous(k: int) -> bool:
+    """The probe operands repeat in k with period 35 and sum to zero over one period in every
+    ``(i mod 5, j mod 7)`` class, so at ``K % 35 == 0`` the expected product is 0 everywhere and
+    matrix cores that return zeros would pass the check.  ``GpuProbe`` and ``odh-gpu-probe``
+    refuse such shapes; the kernels themselves take them."""
+    return k % 35 == 0
+
+
 def gemm_bf16(a, bt, out=None, tile_xcd=None, xcd_blocks=None, tile: Optional[int] = None):
     """``C[M,N] = A[M,K] · Bt[N,K]ᵀ`` in fp32 on the matrix cores.
 
@@ -208,6 +217,8 @@ class GpuProbe:
 
         if not gemm_shape_ok(m, n, k):
             raise ValueError("probe GEMM shape must be tile aligned")
+        if probe_check_vacuous(k):
+            raise ValueError("probe GEMM K must not be a multiple of 35: the expected product is all zero")
         if hbm_bytes < 16 or hbm_bytes % 16:
             raise ValueError("hbm_bytes must be a positive multiple of 16")
         self.device = torch.device("cuda", device)

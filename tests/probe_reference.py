@@ -1,0 +1,121 @@
+"""Host model of the probe kernels (``ops/csrc/gpu_probe.hip``), in numpy and plain Python.
+
+Written from the formulas the kernel comments state, not by calling the library: the HBM
+pattern (``mix32`` / ``pattern16``), the integer-valued probe operands and their product, the
+device-side seed LCG of the graph path, and one iteration of ``busy_kernel`` through the
+operand and C/D layouts of ``v_mfma_f32_32x32x16_bf16``.  Everything here is integer
+arithmetic (or float64 on integers far below 2^53), so the GPU tests compare bit-exactly.
+"""
+
+import numpy as np
+
+N_XCD = 8
+PERIOD = 35  # lcm(5, 7): the probe operands repeat in k with this period
+
+
+# ------------------------------------------------------------------ HBM pattern
+
+
+def mix32(x):
+    """The 32-bit finaliser of the pattern, elementwise on uint32 (wraps modulo 2^32)."""
+    x = np.array(x, dtype=np.uint32, copy=True)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def pattern_words(n16, seed):
+    """The ``4 * n16`` uint32 words of pattern elements 0 .. n16-1: element ``i`` is
+    ``mix32(b), mix32(b + 1), mix32(b + 2), mix32(b + 3)`` with ``b = uint32(4 i) ^ seed``."""
+    i = np.arange(n16, dtype=np.uint64)
+    b = ((i * np.uint64(4)) & np.uint64(0xFFFFFFFF)).astype(np.uint32) ^ np.uint32(seed & 0xFFFFFFFF)
+    words = np.empty((n16, 4), dtype=np.uint32)
+    for lane in range(4):
+        words[:, lane] = mix32(b + np.uint32(lane))  # uint32 addition wraps
+    return words.reshape(-1)
+
+
+def lcg(seed):
+    """One step of the graph path's on-device seed."""
+    return (seed * 1664525 + 1013904223) & 0xFFFFFFFF
+
+
+# ------------------------------------------------------------------ probe GEMM
+
+
+def probe_operands(m, n, k):
+    """``A[i][k] = ((3i + 7k) mod 5) - 2`` and ``Bt[j][k] = ((11j + 5k) mod 7) - 3`` as int64."""
+    kk = np.arange(k, dtype=np.int64)[None, :]
+    a = (3 * np.arange(m, dtype=np.int64)[:, None] + 7 * kk) % 5 - 2
+    bt = (11 * np.arange(n, dtype=np.int64)[:, None] + 5 * kk) % 7 - 3
+    return a, bt
+
+
+def probe_expected(m, n, k):
+    """``A · Btᵀ`` of the probe operands as an exact int64 product."""
+    a, bt = probe_operands(m, n, k)
+    return a @ bt.T
+
+
+def probe_class_table(k):
+    """The closed form: the 5 × 7 table ``t`` with ``C[i][j] = t[i mod 5][j mod 7]``.
+
+    Both operands have period 35 in k, so with ``K = 35 q + rem`` the first ``rem`` residues
+    of k occur ``q + 1`` times and the others ``q`` times."""
+    q, rem = divmod(k, PERIOD)
+    t = np.zeros((5, 7), dtype=np.int64)
+    for i in range(5):
+        for j in range(7):
+            t[i, j] = sum((q + (1 if r < rem else 0)) * ((3 * i + 7 * r) % 5 - 2) * ((11 * j + 5 * r) % 7 - 3)
+                          for r in range(PERIOD))
+    return t
+
+
+def probe_expected_closed_form(m, n, k):
+    t = probe_class_table(k)
+    return t[np.arange(m)[:, None] % 5, np.arange(n)[None, :] % 7]
+
+
+def zero_classes(k):
+    """How many of the 35 ``(i mod 5, j mod 7)`` classes expect 0: the check cannot tell a
+    correct product from an all-zero one there."""
+    return int((probe_class_table(k) == 0).sum())
+
+
+def fused_tile_id(tm, tn, tiles_m, tiles_n, gm=1):
+    """The tile id (index into ``tile_xcd``) that computes output tile ``(tm, tn)`` in the 256²
+    kernels: row-major, or with grouping ``gm`` (when it divides ``tiles_m``) consecutive ids
+    walking ``gm`` tile-rows before the next column of the band."""
+    if gm > 1 and tiles_m % gm == 0:
+        return (tm // gm) * gm * tiles_n + tn * gm + tm % gm
+    return tm * tiles_n + tn
+
+
+# ------------------------------------------------------------------ busy kernel
+
+
+def busy_expected():
+    """Per-lane output (64 values) of one ``busy_kernel`` iteration.
+
+    Each lane holds ``a[e] = (lane + e) & 3`` and ``b[e] = (3 lane + e) & 3``.  As the first or
+    second MFMA operand a register vector is a 32 × 16 matrix: row (first operand) or column
+    (second) ``lane & 31``, ``k = 8 (lane >> 5) + e``.  The four accumulators are ``a·b``,
+    ``b·a``, ``a·a`` and ``b·b``; a lane's 16 result registers are column ``lane & 31``, rows
+    ``(reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)``, and the kernel stores their sum."""
+    va = np.zeros((32, 16), dtype=np.int64)  # [row or column][k]
+    vb = np.zeros((32, 16), dtype=np.int64)
+    for lane in range(64):
+        for e in range(8):
+            va[lane & 31, 8 * (lane >> 5) + e] = (lane + e) & 3
+            vb[lane & 31, 8 * (lane >> 5) + e] = (lane * 3 + e) & 3
+    # D[row][col] = sum_k first[row][k] * second[col][k]
+    d = va @ vb.T + vb @ va.T + va @ va.T + vb @ vb.T
+    out = np.zeros(64, dtype=np.int64)
+    for lane in range(64):
+        col = lane & 31
+        for reg in range(16):
+            out[lane] += d[(reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), col]
+    return out

@@ -211,6 +211,19 @@ def test_probe_program_usage_and_no_gpu_verdict(tmp_path):
     assert r.stdout == ""  # --quiet: the verdict only in the termination log
 
 
+def test_probe_program_refuses_a_vacuous_shape():
+    """At ``K % 35 == 0`` the closed-form expectation is 0 for every output element: a GPU
+    whose matrix cores return zeros would pass, so the shape is a usage error."""
+    exe = _exe()
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="")
+    for shape in ("256,256,2240", "4096,4096,4480"):
+        r = subprocess.run([exe, "--json", "-", "--shape", shape], capture_output=True, text=True, env=env, timeout=60)
+        assert r.returncode == probe_main.USAGE and r.stdout == "", (shape, r.stdout, r.stderr)
+    # the same tiles at the next K step are a shape like any other: no GPU here, not usage
+    r = subprocess.run([exe, "--json", "-", "--shape", "256,256,2304"], capture_output=True, env=env, timeout=60)
+    assert r.returncode == probe_main.NO_GPU
+
+
 def test_probe_python_module_is_torch_free():
     code = ("import sys; from odh_kubeflow_amd.ops import probe_main; rc = probe_main.run(['--json', '-']); "
             "print('TORCH' if 'torch' in sys.modules else 'NOTORCH'); sys.exit(rc)")
