@@ -29,12 +29,28 @@
 // (so each resource's events are in resourceVersion order), and the garbage collector's
 // owner / uid indexes under a short lock of their own; cross-resource work (GC cascades,
 // foreground-deletion owners) runs after the commit, each object under its own resource's
-// lock.  A per-resource history lock the watch threads wait, wake and scan under (a watcher
-// is woken only for events its namespace / selector admits); every stored object is an
-// immutable shared snapshot, so readers and watchers never copy under a lock and each watch
-// event is serialised once.  The watch history is bounded per resource (--history events;
-// a namespace's history is the subsequence of its resource's, trimmed with it and dropped
-// once empty and unwatched), so memory does not grow with the number of namespaces.
+// lock.  Every stored object is an immutable shared snapshot, so readers and watchers never
+// copy under a lock, and each committed version is serialised once: the bytes are the
+// object of its watch line and the body of the write's response, shared, not copied.  The
+// watch history is bounded per resource (--history events; a namespace's history is the
+// subsequence of its resource's, trimmed with it and dropped once empty and unwatched), so
+// memory does not grow with the number of namespaces.
+//
+// Watch delivery: the committing thread delivers.  Once its commit has released the store lock
+// and its own request is answered, it writes the event to each live watcher whose namespace /
+// selector admits it: no futex wake and no context switch between a commit and its watchers.
+// Per watcher a delivery mutex serialises everything written to its socket; whoever holds it
+// drains the watcher's history from where the watcher stands to the end, so each watcher gets
+// its resource's events in resourceVersion order, no gaps and no duplicates, even when two
+// committers reach their watchers in the opposite order of their commits.  A commit never
+// waits for a watcher: committers try-lock, send with MSG_DONTWAIT, park what the socket does
+// not take in the slot's backlog, and leave a busy or backlogged slot to the watch's own
+// thread.  That thread — one per stream, as before — sends the initial list or replay, then
+// sleeps on the per-resource history lock's condition; it wakes to flush a backlog with
+// blocking sends, to catch up (events that arrived while the slot was busy; a
+// selector-filtered watcher's periodic scan), to answer 410 Gone, for bookmarks, the timeout,
+// and to notice a client that has gone.  It owns the fd: a committer whose send fails only
+// marks the slot dead, and the slot is unregistered under both locks before the fd is closed.
 //
 // --write-latency-ms D adds D ms to every write before it commits (outside any lock): an
 // etcd-like storage round trip, for measurements that should not assume a free store.
@@ -483,18 +499,24 @@ Value apply_json_patch(Value doc, const Value& ops) {
   return doc;
 }
 
+// RFC 7386 in place: only what the patch replaces is allocated
+void merge_patch_in(Value& target, const Value& patch) {
+  if (!patch.is_obj()) {
+    target = patch;
+    return;
+  }
+  if (!target.is_obj()) target = Value::object();
+  for (auto& m : patch.obj) {
+    if (m.v.is_null()) target.erase(m.k);
+    else if (m.v.is_obj()) merge_patch_in(target[m.k], m.v);
+    else target[m.k] = m.v;
+  }
+}
+
 Value merge_patch(const Value& target, const Value& patch) {
   if (!patch.is_obj()) return patch;
   Value out = target.is_obj() ? target : Value::object();
-  for (auto& m : patch.obj) {
-    if (m.v.is_null()) out.erase(m.k);
-    else if (m.v.is_obj()) {
-      const Value* cur = out.get(m.k);
-      out[m.k] = merge_patch(cur ? *cur : Value(), m.v);
-    } else {
-      out[m.k] = m.v;
-    }
-  }
+  merge_patch_in(out, patch);
   return out;
 }
 
@@ -559,10 +581,15 @@ Value strategic_patch(const Value& target, const Value& patch) {
 
 using Obj = std::shared_ptr<const Value>;
 
+// One event's watch lines, serialised once per API version and shared (never copied) by every
+// watcher and by the committing request's own response: a line is
+// {"type":"<TYPE>","object":<object>}\n, and <object> is the response body of the write.
+using Line = std::shared_ptr<const std::string>;
 struct EvCache {
   std::mutex mu;
-  std::string version;
-  std::shared_ptr<std::string> line;
+  Line line;            // the storage version's
+  std::string version;  // one other version's (Notebook v1 / v1alpha1 against v1beta1 storage)
+  Line vline;
 };
 
 struct Ev {
@@ -576,6 +603,7 @@ struct Ev {
 };
 
 struct Hist;
+struct Bucket;
 
 struct WatchSlot {
   std::condition_variable cv;
@@ -587,10 +615,26 @@ struct WatchSlot {
   // is not woken by them and could fall behind the bounded history — the periodic wake-up
   // (emit) advances it; a watch without one is woken by every event it reads
   bool filtered = false;
-  // the history it reads and the seq it has scanned up to (both under the bucket's hmu): the
-  // periodic wake-up skips a watcher with nothing unscanned
-  const Hist* hist = nullptr;
+  // the history it reads and the seq it has scanned up to: the periodic wake-up skips a
+  // watcher with nothing unscanned.  `seen` is written under the bucket's hmu AND dmu (so
+  // either lock suffices to read it): the stream thread's wait predicate reads it under hmu,
+  // a delivery continues from it under dmu
+  Hist* hist = nullptr;
   int64_t seen = 0;
+  // Delivery.  Whoever holds `dmu` — a committing request thread (try_lock, non-blocking
+  // sends) or the stream's own thread (blocking) — drains the history from `seen` to its end
+  // into the socket, so the events reach the watcher in order whichever thread carries them
+  // and chunks never interleave.  Bytes a committer could not send without blocking wait in
+  // `backlog`; while it is non-empty committers leave the slot to its stream thread.
+  std::mutex dmu;
+  Bucket* bucket = nullptr;
+  const Res* res = nullptr;
+  std::string version, ns;
+  int fd = -1;              // under dmu; -1 once the stream has unregistered (it owns and closes the fd)
+  std::string backlog;      // under dmu
+  std::atomic<bool> dead{false};     // a send failed: the stream thread ends the watch
+  std::atomic<bool> pending{false};  // backlog to flush: the stream thread's wait predicate
+  std::atomic<uint64_t> last_write_ns{0};  // mono_ns of the last bytes sent, by whichever thread (bookmark pacing)
 };
 
 // one ordered event history: `seq` numbers its events, `hist` keeps the newest S.history
@@ -621,6 +665,9 @@ struct Bucket {
   // this resource's store lock: objs, and the commit order of its events
   std::mutex mu;
   std::atomic<uint64_t> wait_ns{0}, contended{0};  // contended acquisitions of mu (GET /metrics "locks")
+  // bumped by every event of the resource (inside its commit): what is derived from the
+  // resource's objects — the admission webhook cache — is valid for one value of it
+  std::atomic<int64_t> gen{0};
 };
 
 struct Store {
@@ -662,8 +709,17 @@ struct Prof {
   std::atomic<uint64_t> trim_ns{0}, trim_max_ns{0}, trims{0};  // malloc_trim passes (allocations wait on them)
   std::atomic<uint64_t> webhook_dials{0}, webhook_dial_ns{0};  // new webhook connections: connect + TLS handshake
   std::atomic<uint64_t> watch_gone{0};  // watches answered 410 Gone (behind the bounded history): each is a relist
+  // delivery passes that wrote events to a watcher (`wakeups` counts both): by the committing
+  // request thread itself, or left to the watch stream's own thread (slot busy or backlogged,
+  // socket full, catch-up of a filtered watcher)
+  std::atomic<uint64_t> direct{0}, fallback{0};
+  std::atomic<uint64_t> backlogged{0};  // committer sends that would have blocked (the rest went to the backlog)
+  std::atomic<int64_t> slots{0};        // watch streams registered right now (a gauge)
 } P;
 thread_local int t_cat = C_OTHER;
+// thread CPU this request thread spent delivering watch events since the request began: booked
+// to the watch class as it accrues, and taken off the request's own class (serve_conn)
+thread_local uint64_t t_deliver_ns = 0;
 
 // thread CPU per phase of the write path (GET /metrics "phases"): where a write's CPU goes
 enum Phase { PH_PARSE, PH_ADMIT, PH_VALIDATE, PH_DEFAULTS, PH_PATCH, PH_PREPARE, PH_DUMP, PH_N };
@@ -707,12 +763,13 @@ uint64_t mono_ns() {
 }
 
 // the store lock on the request path, timing only the contended acquisitions
-// Watcher wake-ups are decided and delivered after the store lock is released: emit()
-// (which runs inside a commit) only queues the candidate watchers of the event on this
-// thread; ~StoreLock evaluates their filters and notifies them once the lock is free, so
-// the lock covers the commit alone (with one shard per GPU a pod write has a candidate
-// per node-agent watch).  No wake-up is lost: the event is published (seq bumped) under
-// the history lock before the notify, and a waiter re-checks seq under that lock.
+// Deliveries are decided and made after the store lock is released: emit() (which runs
+// inside a commit) only queues the candidate watchers of the event on this thread;
+// ~StoreLock evaluates their filters and delivers to them (flush_wakes) once the lock is
+// free, so the lock covers the commit alone (with one shard per GPU a pod write has a
+// candidate per node-agent watch).  No event is lost: it is published (seq bumped) under
+// the history lock before any delivery or notify, a delivery drains the history, and a
+// waiting stream thread re-checks seq under that lock.
 struct PendingWake {
   std::shared_ptr<WatchSlot> w;
   Obj obj, old;
@@ -723,7 +780,7 @@ thread_local std::vector<PendingWake> t_wake;
 // object version, whose tree is freed once the store lock is released (~StoreLock), not
 // while every other writer of the resource waits for it
 thread_local std::vector<Ev> t_free;
-thread_local std::vector<std::shared_ptr<std::string>> t_free_lines;
+thread_local std::vector<Line> t_free_lines;
 // an event's serialised watch line is dropped this many events after it was emitted: every
 // live watcher has written it by then (they are woken at once); a late reader re-serialises.
 // The history keeps the objects (shared with the store) but not a second, JSON copy of each
@@ -736,12 +793,41 @@ thread_local std::vector<std::string> t_gc;
 thread_local bool t_gc_running = false;
 void run_gc() noexcept;
 
+// A write is answered first and its events are delivered right after (serve_conn flushes once
+// the response is out).  Watchers first — the order of the wake-up and the response before the
+// committing thread delivered — now puts the event into the writer's own informer ahead of the
+// response every time, and the closed loop then runs 33 writes and 10 reconciles per notebook
+// where it ran 34 and 9: the benchmark's workload would not be the same.
+// ODH_APISERVER_WATCHERS_FIRST=1 (measurements) restores that order.
+bool g_respond_first = true;
+
+// The events this request thread committed (emit), so that the response reuses the
+// serialisation of the watch line: cleared per request (serve_conn)
+struct Emitted {
+  const Value* obj;
+  const char* type;
+  std::shared_ptr<EvCache> cache;
+};
+thread_local std::vector<Emitted> t_emitted;
+
+void deliver_committed(WatchSlot& s);
+
+// The committing thread, store lock released and (by default) its response sent: it carries
+// the event to each live watcher that wants it (deliver_committed: never blocks) — no futex wake, context switch and scheduler
+// latency between a commit and its watchers.  A periodic catch-up wake (`all`) only notifies.
 void flush_wakes() {
   std::vector<PendingWake> ws;
   ws.swap(t_wake);
+  const uint64_t c0 = thread_cpu_ns();
   for (auto& p : ws) {
     WatchSlot* w = p.w.get();
-    if (p.all || !w->wants || w->wants(*p.obj) || (p.old && w->wants(*p.old))) w->cv.notify_all();
+    if (p.all) w->cv.notify_all();
+    else if (!w->wants || w->wants(*p.obj) || (p.old && w->wants(*p.old))) deliver_committed(*w);
+  }
+  if (t_cat != C_WATCH) {
+    const uint64_t d = thread_cpu_ns() - c0;
+    P.cpu_ns[C_WATCH] += d;
+    t_deliver_ns += d;
   }
 }
 
@@ -765,7 +851,7 @@ struct StoreLock {
     mu.unlock();
     if (!t_free.empty()) t_free.clear();
     if (!t_free_lines.empty()) t_free_lines.clear();
-    if (!t_wake.empty()) flush_wakes();
+    if (!t_wake.empty() && !g_respond_first) flush_wakes();
     if ((!t_gc.empty() || !t_fg.empty()) && !t_gc_running) run_gc();
   }
   StoreLock(const StoreLock&) = delete;
@@ -862,7 +948,10 @@ void emit(const Res& r, const char* type, Obj obj, Obj old) {
   if (b.all.hist.size() > kLineKeep) {
     EvCache& c = *b.all.hist[b.all.hist.size() - 1 - kLineKeep].cache;
     std::unique_lock<std::mutex> cl(c.mu, std::try_to_lock);  // a watcher serialising it: next time
-    if (cl.owns_lock() && c.line) t_free_lines.push_back(std::move(c.line));
+    if (cl.owns_lock()) {
+      if (c.line) t_free_lines.push_back(std::move(c.line));
+      if (c.vline) t_free_lines.push_back(std::move(c.vline));
+    }
   }
   if (g_stall_ms > 0) {
     const uint64_t now = mono_ns();
@@ -870,6 +959,8 @@ void emit(const Res& r, const char* type, Obj obj, Obj old) {
     if (!evns.empty()) b.by_ns[evns].hist.back().t_ns = now;
   }
   const Ev& ev = b.all.hist.back();
+  b.gen.fetch_add(1, std::memory_order_release);
+  t_emitted.push_back({ev.obj.get(), type, ev.cache});
   const int64_t step = std::max<int64_t>(1, (int64_t)S.history / 16);
   if (b.all.seq % step == 0) {
     // periodic wake-up of the selector-filtered watchers, an eighth of them every history/16
@@ -895,10 +986,11 @@ void emit(const Res& r, const char* type, Obj obj, Obj old) {
   if (!ns.empty()) wake("");
 }
 
-Value out_obj(const Res& r, const Value& o, const std::string& version) {
-  Value c = o;
-  if (!version.empty() && version != r.storage) c["apiVersion"] = Value::str(r.api_version(version));
-  return c;
+// `o` as the requested API version: a non-storage version differs in apiVersion only, so it
+// is written with that one member overridden — no copy of the tree
+void dump_version(std::string& out, const Res& r, const Value& o, const std::string& version) {
+  if (version.empty() || version == r.storage) kj::dump(out, o);
+  else kj::dump_with(out, o, "apiVersion", r.api_version(version));
 }
 
 // a and b agree on every member not named in skip (object members in any order); no copies
@@ -934,13 +1026,13 @@ bool equal_except_meta(const Value& a, const Value& b) {
   return members_equal_except(*ma, *mb, {"resourceVersion", "managedFields", "generation"});
 }
 
-Value out_obj(const Res& r, const Value& o, const std::string& version);
-
-// the response body of a write: no copy when the request used the storage version
+// the response body of a read (a write's is its watch line's object: respond_committed)
 std::string dump_out(const Res& r, const Value& o, const std::string& version) {
   PhaseTimer pt(PH_DUMP);
-  if (version.empty() || version == r.storage) return kj::dump(o);
-  return kj::dump(out_obj(r, o, version));
+  std::string s;
+  s.reserve(512);
+  dump_version(s, r, o, version);
+  return s;
 }
 
 // ------------------------------------------------------------------ CRD structural schemas
@@ -1430,6 +1522,8 @@ void defaults(const Res& r, Value& o, bool api = true) {
 
 // ------------------------------------------------------------------ admission (MutatingWebhookConfiguration)
 
+struct CelNode;
+
 struct Webhook {
   std::string name, url_host, url_path, ca_pem, svc_ns, svc_name, svc_path;
   int url_port = 443, svc_port = 443;
@@ -1438,7 +1532,13 @@ struct Webhook {
   Value rules;
   bool has_ns_sel = false, has_obj_sel = false;
   std::vector<LReq> ns_sel, obj_sel;
-  std::vector<std::string> conditions;  // matchConditions[].expression
+  // matchConditions[].expression, compiled once when the configuration is read (webhooks_for's
+  // cache): the tree, or the compile error every evaluation reports
+  struct Cond {
+    std::shared_ptr<const CelNode> node;
+    std::string err;
+  };
+  std::vector<Cond> conditions;
 };
 
 // ------------------------------------------------------------------ matchConditions (a CEL subset)
@@ -1589,9 +1689,14 @@ bool cel_eval(const CelNode& n, const Value& obj, const Value* old) {
 bool conditions_allow(const Webhook& w, const Value& obj, const Value* old) {
   bool failed = false;
   std::string msg;
-  for (const std::string& c : w.conditions) {
+  for (const Webhook::Cond& c : w.conditions) {
+    if (!c.node) {
+      failed = true;
+      msg = c.err;
+      continue;
+    }
     try {
-      if (!cel_eval(CelParser(c).parse(), obj, old)) return false;
+      if (!cel_eval(*c.node, obj, old)) return false;
     } catch (const CelErr& e) {
       failed = true;
       msg = e.msg;
@@ -1660,14 +1765,14 @@ std::string b64decode(const std::string& in) {
   return out;
 }
 
-std::vector<Webhook> webhooks_for(const Res& r, const std::string& op) {
+// The webhooks whose rules match (resource, operation), from the stored
+// MutatingWebhookConfigurations: CA bundles decoded, selectors parsed, conditions compiled.
+std::vector<Webhook> build_webhooks(const Res& r, const std::string& op, Bucket& mb) {
   std::vector<Webhook> out;
-  Res* mwc = by_kind("admissionregistration.k8s.io", "MutatingWebhookConfiguration");
-  if (!mwc) return out;
   std::vector<Obj> cfgs;
   {
-    StoreLock g(bucket(*mwc));
-    for (auto& kv : bucket(*mwc).objs) cfgs.push_back(kv.second);
+    StoreLock g(mb);
+    for (auto& kv : mb.objs) cfgs.push_back(kv.second);
   }
   for (auto& c : cfgs) {
     const Value* whs = c->get("webhooks");
@@ -1692,7 +1797,15 @@ std::vector<Webhook> webhooks_for(const Res& r, const std::string& op) {
         }
       if (const Value* mc = wh.get("matchConditions"))
         if (mc->is_arr())
-          for (auto& c : mc->arr) w.conditions.push_back(c.str_or("expression"));
+          for (auto& c : mc->arr) {
+            Webhook::Cond cond;
+            try {
+              cond.node = std::make_shared<const CelNode>(CelParser(c.str_or("expression")).parse());
+            } catch (const CelErr& e) {
+              cond.err = e.msg;
+            }
+            w.conditions.push_back(std::move(cond));
+          }
       const Value* cc = wh.get("clientConfig");
       if (cc) {
         std::string ca = cc->str_or("caBundle");
@@ -1719,6 +1832,42 @@ std::vector<Webhook> webhooks_for(const Res& r, const std::string& op) {
     }
   }
   return out;
+}
+
+// webhooks_for() runs on every non-status write of every kind, and its answer changes only
+// when a MutatingWebhookConfiguration is written: it is kept per (resource, operation) for one
+// generation of that bucket (Bucket::gen, bumped inside every commit of the resource).  The
+// generation is read BEFORE the objects, so an entry may hold newer objects than its
+// generation says — it is then rebuilt by the next call — never older ones.  Endpoints are not
+// cached: resolve_service reads them on each call that goes out.
+using Webhooks = std::shared_ptr<const std::vector<Webhook>>;
+struct WebhookCache {
+  std::mutex mu;
+  int64_t gen = -1;
+  std::map<std::pair<const Res*, std::string>, Webhooks> by_key;
+} g_wh_cache;
+
+Webhooks webhooks_for(const Res& r, const std::string& op) {
+  static const Webhooks none = std::make_shared<const std::vector<Webhook>>();
+  static Res* const mwc = by_kind("admissionregistration.k8s.io", "MutatingWebhookConfiguration");
+  if (!mwc) return none;
+  Bucket& mb = bucket(*mwc);
+  const int64_t gen = mb.gen.load(std::memory_order_acquire);
+  {
+    std::lock_guard<std::mutex> g(g_wh_cache.mu);
+    if (g_wh_cache.gen == gen) {
+      auto it = g_wh_cache.by_key.find({&r, op});
+      if (it != g_wh_cache.by_key.end()) return it->second;
+    }
+  }
+  Webhooks built = std::make_shared<const std::vector<Webhook>>(build_webhooks(r, op, mb));
+  std::lock_guard<std::mutex> g(g_wh_cache.mu);
+  if (g_wh_cache.gen < gen) {  // the first entry of a newer generation drops the older ones
+    g_wh_cache.by_key.clear();
+    g_wh_cache.gen = gen;
+  }
+  if (g_wh_cache.gen == gen) g_wh_cache.by_key[{&r, op}] = built;
+  return built;
 }
 
 std::atomic<uint64_t> g_rr{0};
@@ -1916,14 +2065,13 @@ bool tls_read_response(TlsConn& c, int* status, std::string* body, bool* close =
   return false;
 }
 
-Value call_webhook(const Webhook& w, const Value& review) {
+Value call_webhook(const Webhook& w, const std::string& body) {
   std::string host = w.url_host, path = w.url_path;
   int port = w.url_port;
   if (!w.has_url) {
     if (!resolve_service(w, &host, &port)) throw std::runtime_error("no endpoints for service " + w.svc_ns + "/" + w.svc_name);
     path = w.svc_path;
   }
-  std::string body = kj::dump(review);
   std::string req = "POST " + path + " HTTP/1.1\r\nHost: " + host + ":" + std::to_string(port) +
                     "\r\nContent-Type: application/json\r\nAccept: application/json\r\nContent-Length: " +
                     std::to_string(body.size()) + "\r\n\r\n" + body;
@@ -2019,8 +2167,8 @@ bool selectors_match(const Webhook& w, const Res& r, const Value& obj, const Val
 
 Value admit(const char* op, const Res& r, Value obj, const Value* old) {
   PhaseTimer pt(PH_ADMIT);
-  auto hooks = webhooks_for(r, op);
-  for (auto& w : hooks) {
+  const Webhooks hooks = webhooks_for(r, op);
+  for (auto& w : *hooks) {
     if (!selectors_match(w, r, obj, old)) continue;
     if (!w.conditions.empty() && !conditions_allow(w, obj, old)) continue;
     Value review = Value::object();
@@ -2041,9 +2189,17 @@ Value admit(const char* op, const Res& r, Value obj, const Value* old) {
     res["version"] = Value::str(r.storage);
     res["resource"] = Value::str(r.plural);
     req["resource"] = res;
-    req["object"] = obj;
-    req["oldObject"] = old ? *old : Value();
     review["request"] = std::move(req);
+    // the envelope as a tree, object and oldObject written straight into its last member
+    // (neither is copied into the review)
+    std::string body = kj::dump(review);
+    body.resize(body.size() - 2);  // the closing braces of request and of the review
+    body += ",\"object\":";
+    kj::dump(body, obj);
+    body += ",\"oldObject\":";
+    if (old) kj::dump(body, *old);
+    else body += "null";
+    body += "}}";
     S.webhook_calls++;
     Value out;
     uint64_t t_admit = mono_ns();
@@ -2057,7 +2213,7 @@ Value admit(const char* op, const Res& r, Value obj, const Value* old) {
       }
     } admit_timer{t_admit};
     try {
-      out = call_webhook(w, review);
+      out = call_webhook(w, body);
     } catch (const std::exception& e) {
       if (w.fail_closed) throw Internal("failed calling webhook \"" + w.name + "\": " + e.what());
       continue;
@@ -2323,6 +2479,28 @@ Obj do_patch_once(const Res& r, const std::string& ns, const std::string& name, 
     if (it == bucket(r).objs.end()) throw NotFound(r.err_res(), name);
     cur = it->second;
   }
+  const Value* pm = patch.is_obj() ? patch.get("metadata") : nullptr;
+  bool precond = pm && pm->is_obj() && !pm->str_or("resourceVersion").empty();
+  if (sub == "status" && ptype == "merge" && patch.is_obj()) {
+    // The status subresource takes the patched status (and a resourceVersion precondition)
+    // and nothing else, so a merge patch is applied to that member of ONE copy of the stored
+    // object; the general path below patches a copy whole and then copies the stored object
+    // a second time to put the status into.
+    Value nw;
+    {
+      PhaseTimer pt(PH_PATCH);
+      nw = *cur;
+      if (const Value* ps = patch.get("status")) {
+        if (ps->is_null()) nw["status"] = Value();
+        else merge_patch_in(nw["status"], *ps);
+      } else if (!nw.get("status")) {
+        nw["status"] = Value();
+      }
+      if (precond) mdm(nw)["resourceVersion"] = Value::str(pm->str_or("resourceVersion"));
+    }
+    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    return commit_update(r, cur, std::move(nw));
+  }
   Value nw;
   try {
     PhaseTimer pt(PH_PATCH);
@@ -2333,8 +2511,6 @@ Obj do_patch_once(const Res& r, const std::string& ns, const std::string& name, 
   } catch (const PatchErr& e) {
     throw Invalid(r.kind, name, e.msg);
   }
-  const Value* pm = patch.is_obj() ? patch.get("metadata") : nullptr;
-  bool precond = pm && pm->is_obj() && !pm->str_or("resourceVersion").empty();
   if (!precond) mdm(nw)["resourceVersion"] = Value::str(mget(*cur, "resourceVersion"));
   if (sub == "status") {
     Value merged = *cur;
@@ -2723,10 +2899,58 @@ void audit_write(const AuditCtx& a, const std::string& uri, const std::string& u
   }
 }
 
-bool respond(int fd, int code, const std::string& body, bool keep_alive) {
+// Everything in iov[0..n) in as few sendmsg calls as it takes — no concatenation into one
+// buffer.  With MSG_DONTWAIT in `flags` it stops where the socket would block: iov / n then
+// say what is left (n > 0).  False: the send failed (the peer is gone).
+bool send_iov(int fd, struct iovec*& iov, int& n, int flags) {
+  while (n > 0) {
+    struct msghdr mh {};
+    mh.msg_iov = iov;
+    mh.msg_iovlen = (size_t)std::min(n, 1024);
+    ssize_t w = sendmsg(fd, &mh, flags | MSG_NOSIGNAL);
+    if (w < 0) {
+      if (errno == EINTR) continue;
+      if ((flags & MSG_DONTWAIT) && (errno == EAGAIN || errno == EWOULDBLOCK)) return true;
+      return false;
+    }
+    size_t left = (size_t)w;
+    while (n > 0 && left >= iov->iov_len) {
+      left -= iov->iov_len;
+      ++iov;
+      --n;
+    }
+    if (n > 0) {
+      if (w == 0) return false;
+      iov->iov_base = (char*)iov->iov_base + left;
+      iov->iov_len -= left;
+    }
+  }
+  return true;
+}
+
+// The request's CPU and its call are booked BEFORE its response leaves: a client that has its
+// answer, reading /metrics on another connection, finds the request counted.  What the thread
+// spends afterwards (the send itself) is added by serve_conn; CPU it spent delivering watch
+// events belongs to the watch class (flush_wakes) and is taken off here.
+thread_local uint64_t t_req_c0 = 0;
+thread_local bool t_counted = false;
+void book_request() {
+  if (t_cat == C_WATCH) return;  // a watch books its own CPU as it goes
+  const uint64_t now = thread_cpu_ns();
+  const uint64_t d = now - t_req_c0;
+  P.cpu_ns[t_cat] += d > t_deliver_ns ? d - t_deliver_ns : 0;
+  t_req_c0 = now;
+  t_deliver_ns = 0;
+  if (!t_counted) {
+    P.calls[t_cat]++;
+    t_counted = true;
+  }
+}
+
+bool respond(int fd, int code, std::string_view body, bool keep_alive) {
   if (t_aud.on) {
     t_aud.code = code;
-    if (t_aud.level == "RequestResponse") t_aud.resp = body;
+    if (t_aud.level == "RequestResponse") t_aud.resp = std::string(body);
     if (t_aud.name.empty() && t_aud.verb == "create" && code < 300) {
       // kube-apiserver names the created object in objectRef (generateName included)
       try {
@@ -2736,71 +2960,134 @@ bool respond(int fd, int code, const std::string& body, bool keep_alive) {
       }
     }
   }
-  std::string h = "HTTP/1.1 " + std::to_string(code) + " " + reason_phrase(code) +
-                  "\r\nContent-Type: application/json\r\nContent-Length: " + std::to_string(body.size()) +
-                  (keep_alive ? "\r\n\r\n" : "\r\nConnection: close\r\n\r\n");
-  h += body;
-  return write_all(fd, h.data(), h.size());
+  book_request();
+  char h[160];
+  int hl = snprintf(h, sizeof(h), "HTTP/1.1 %d %s\r\nContent-Type: application/json\r\nContent-Length: %zu\r\n%s\r\n", code,
+                    reason_phrase(code), body.size(), keep_alive ? "" : "Connection: close\r\n");
+  struct iovec iov[2] = {{h, (size_t)hl}, {const_cast<char*>(body.data()), body.size()}};
+  struct iovec* p = iov;
+  int n = 2;
+  return send_iov(fd, p, n, 0);
 }
+
+// the query parameters in request order (a handful: no tree); a repeated key keeps its last value
+struct Query {
+  std::vector<std::pair<std::string, std::string>> kv;
+  const std::string* find(std::string_view k) const {
+    for (auto& e : kv)
+      if (e.first == k) return &e.second;
+    return nullptr;
+  }
+  size_t count(std::string_view k) const { return find(k) ? 1 : 0; }
+  const std::string& at(std::string_view k) const {
+    const std::string* v = find(k);
+    if (!v) throw std::out_of_range("query parameter");
+    return *v;
+  }
+  void set(std::string k, std::string v) {
+    for (auto& e : kv)
+      if (e.first == k) {
+        e.second = std::move(v);
+        return;
+      }
+    kv.emplace_back(std::move(k), std::move(v));
+  }
+};
 
 struct Request {
   std::string method, path, query, body, ctype, auth, user_agent, target;
   bool keep_alive = true;
-  std::map<std::string, std::string> q;
+  Query q;
 };
 
+std::string url_decode(std::string_view s) {
+  if (s.find_first_of("%+") == std::string_view::npos) return std::string(s);
+  return url_decode(std::string(s));
+}
+
+std::string_view trim_view(std::string_view s) {
+  size_t a = s.find_first_not_of(" \t"), b = s.find_last_not_of(" \t");
+  return a == std::string_view::npos ? std::string_view() : s.substr(a, b - a + 1);
+}
+
+bool iequal(std::string_view a, const char* lower) {
+  size_t n = strlen(lower);
+  if (a.size() != n) return false;
+  for (size_t k = 0; k < n; ++k)
+    if (std::tolower((unsigned char)a[k]) != lower[k]) return false;
+  return true;
+}
+
+// the head is parsed in place (views into the connection buffer, no streams), and a body that
+// ends the buffer — every request of a client that does not pipeline — is moved out of it
 bool read_request(Conn& c, Request& rq) {
   char tmp[65536];
   size_t hdr_end;
-  while ((hdr_end = c.buf.find("\r\n\r\n")) == std::string::npos) {
+  size_t scan = 0;
+  while ((hdr_end = c.buf.find("\r\n\r\n", scan)) == std::string::npos) {
+    scan = c.buf.size() < 3 ? 0 : c.buf.size() - 3;
     ssize_t n = recv(c.fd, tmp, sizeof(tmp), 0);
     if (n <= 0) return false;
     c.buf.append(tmp, n);
     if (c.buf.size() > (64u << 20)) return false;
   }
-  std::string head = c.buf.substr(0, hdr_end);
-  c.buf.erase(0, hdr_end + 4);
-  std::istringstream hs(head);
-  std::string line;
-  std::getline(hs, line);
-  if (!line.empty() && line.back() == '\r') line.pop_back();
-  std::istringstream ls(line);
-  std::string target, proto;
-  ls >> rq.method >> target >> proto;
-  rq.target = target;
-  size_t qm = target.find('?');
-  rq.path = url_decode(target.substr(0, qm));
-  rq.query = qm == std::string::npos ? "" : target.substr(qm + 1);
-  for (auto& kv : split(rq.query, '&')) {
-    if (kv.empty()) continue;
-    size_t e = kv.find('=');
-    rq.q[url_decode(kv.substr(0, e))] = e == std::string::npos ? "" : url_decode(kv.substr(e + 1));
-  }
   size_t clen = 0;
   bool chunked = false;
-  rq.keep_alive = proto != "HTTP/1.0";
-  while (std::getline(hs, line)) {
-    if (!line.empty() && line.back() == '\r') line.pop_back();
-    size_t colon = line.find(':');
-    if (colon == std::string::npos) continue;
-    std::string k = line.substr(0, colon), v = trim(line.substr(colon + 1));
-    std::transform(k.begin(), k.end(), k.begin(), ::tolower);
-    if (k == "content-length") {
-      // digits only: a malformed length ends the connection instead of throwing out of the
-      // connection thread (which would terminate the server)
-      if (v.empty() || v.size() > 12 || v.find_first_not_of("0123456789") != std::string::npos) return false;
-      clen = std::stoul(v);
+  {
+    const std::string_view head(c.buf.data(), hdr_end);
+    size_t eol = head.find('\n');
+    std::string_view line = head.substr(0, eol);
+    if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+    // METHOD SP target SP protocol (blanks of any length between them)
+    std::string_view word[3];
+    size_t at = 0;
+    for (int k = 0; k < 3; ++k) {
+      const char* ws = " \t\r\n\v\f";
+      size_t a = line.find_first_not_of(ws, at);
+      if (a == std::string_view::npos) break;
+      size_t b = line.find_first_of(ws, a);
+      word[k] = line.substr(a, b == std::string_view::npos ? b : b - a);
+      at = b == std::string_view::npos ? line.size() : b;
     }
-    else if (k == "content-type") rq.ctype = v.substr(0, v.find(';'));
-    else if (k == "authorization") rq.auth = v;
-    else if (k == "user-agent") rq.user_agent = v;
-    else if (k == "transfer-encoding" && v.find("chunked") != std::string::npos) chunked = true;
-    else if (k == "connection") {
-      std::string lv = v;
-      std::transform(lv.begin(), lv.end(), lv.begin(), ::tolower);
-      if (lv == "close") rq.keep_alive = false;
+    rq.method = std::string(word[0]);
+    const std::string_view target = word[1];
+    rq.target = std::string(target);
+    size_t qm = target.find('?');
+    rq.path = url_decode(target.substr(0, qm));
+    rq.query = qm == std::string_view::npos ? "" : std::string(target.substr(qm + 1));
+    for (std::string_view rest = rq.query; !rest.empty();) {
+      size_t amp = rest.find('&');
+      std::string_view kv = rest.substr(0, amp);
+      rest = amp == std::string_view::npos ? std::string_view() : rest.substr(amp + 1);
+      if (kv.empty()) continue;
+      size_t e = kv.find('=');
+      rq.q.set(url_decode(kv.substr(0, e)), e == std::string_view::npos ? "" : url_decode(kv.substr(e + 1)));
+    }
+    rq.keep_alive = word[2] != "HTTP/1.0";
+    size_t pos = eol == std::string_view::npos ? head.size() : eol + 1;
+    while (pos < head.size()) {
+      eol = head.find('\n', pos);
+      line = head.substr(pos, eol == std::string_view::npos ? eol : eol - pos);
+      pos = eol == std::string_view::npos ? head.size() : eol + 1;
+      if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+      size_t colon = line.find(':');
+      if (colon == std::string_view::npos) continue;
+      const std::string_view k = line.substr(0, colon), v = trim_view(line.substr(colon + 1));
+      if (iequal(k, "content-length")) {
+        // digits only: a malformed length ends the connection instead of throwing out of the
+        // connection thread (which would terminate the server)
+        if (v.empty() || v.size() > 12 || v.find_first_not_of("0123456789") != std::string_view::npos) return false;
+        clen = 0;
+        for (char ch : v) clen = clen * 10 + (size_t)(ch - '0');
+      }
+      else if (iequal(k, "content-type")) rq.ctype = std::string(v.substr(0, v.find(';')));
+      else if (iequal(k, "authorization")) rq.auth = std::string(v);
+      else if (iequal(k, "user-agent")) rq.user_agent = std::string(v);
+      else if (iequal(k, "transfer-encoding") && v.find("chunked") != std::string_view::npos) chunked = true;
+      else if (iequal(k, "connection") && iequal(v, "close")) rq.keep_alive = false;
     }
   }
+  c.buf.erase(0, hdr_end + 4);
   if (chunked) {
     std::string out;
     while (true) {
@@ -2827,15 +3114,26 @@ bool read_request(Conn& c, Request& rq) {
       out.append(c.buf, 0, sz);
       c.buf.erase(0, sz + 2);
     }
-    rq.body = out;
+    rq.body = std::move(out);
   } else {
-    while (c.buf.size() < clen) {
-      ssize_t n = recv(c.fd, tmp, sizeof(tmp), 0);
-      if (n <= 0) return false;
-      c.buf.append(tmp, n);
+    if (clen > (64u << 20)) return false;
+    if (c.buf.size() < clen) {
+      // straight into the buffer: no bounce through tmp for a large body
+      size_t have = c.buf.size();
+      c.buf.resize(clen);
+      while (have < clen) {
+        ssize_t n = recv(c.fd, &c.buf[have], clen - have, 0);
+        if (n <= 0) return false;
+        have += (size_t)n;
+      }
     }
-    rq.body = c.buf.substr(0, clen);
-    c.buf.erase(0, clen);
+    if (c.buf.size() == clen) {
+      rq.body = std::move(c.buf);
+      c.buf.clear();
+    } else {
+      rq.body.assign(c.buf, 0, clen);
+      c.buf.erase(0, clen);
+    }
   }
   return true;
 }
@@ -2972,29 +3270,159 @@ bool socket_closed(int fd) {
   return false;
 }
 
-bool write_chunk(int fd, const std::string& data) {
-  char hdr[32];
-  int h = snprintf(hdr, sizeof(hdr), "%zx\r\n", data.size());
-  std::string out(hdr, h);
-  out += data;
-  out += "\r\n";
-  return write_all(fd, out.data(), out.size());
+// ------------------------------------------------------------------ watch delivery
+//
+// An event's line is serialised once per API version (EvCache) by whoever needs it first —
+// the committing thread, delivering or answering — and handed out as a shared string.
+
+// {"type":"<TYPE>","object":  — what precedes the object in a line; "}\n" follows it
+size_t line_prefix(const char* type) { return 9 + strlen(type) + 11; }
+
+Line make_line(const Res& r, const char* type, const Value& obj, const std::string& version) {
+  auto s = std::make_shared<std::string>();
+  s->reserve(1024);
+  *s += "{\"type\":\"";
+  *s += type;
+  *s += "\",\"object\":";
+  dump_version(*s, r, obj, version);
+  *s += "}\n";
+  return s;
 }
 
-std::string event_line(const Res& r, const Ev& e, const std::string& version) {
-  auto& c = *e.cache;
+Line event_line(const Res& r, const char* type, const Value& obj, EvCache& c, const std::string& version) {
+  const bool storage = version.empty() || version == r.storage;
   std::lock_guard<std::mutex> g(c.mu);
-  if (c.line && c.version == version) return *c.line;
-  Value ev = Value::object();
-  ev["type"] = Value::str(e.type);
-  ev["object"] = out_obj(r, *e.obj, version);
-  auto s = std::make_shared<std::string>(kj::dump(ev));
-  *s += '\n';
-  if (!c.line) {
+  if (storage) {
+    if (c.line) return c.line;
+  } else if (c.vline && c.version == version) {
+    return c.vline;
+  }
+  Line s = make_line(r, type, obj, version);
+  if (storage) {
     c.line = s;
+  } else if (!c.vline) {
+    c.vline = s;
     c.version = version;
   }
-  return *s;
+  return s;
+}
+
+Line error_line(const ApiErr& e) {
+  Value ev = Value::object();
+  ev["type"] = Value::str("ERROR");
+  ev["object"] = status_obj(e);
+  return std::make_shared<const std::string>(kj::dump(ev) + "\n");
+}
+
+// Publish a flag the stream thread's wait predicate reads (pending, dead): passing through the
+// history lock it waits under means it either saw the flag or is already waiting.
+void wake_stream(WatchSlot& s) {
+  { std::lock_guard<std::mutex> hg(s.bucket->hmu); }
+  s.cv.notify_all();
+}
+
+constexpr size_t kChunkLines = 512;  // lines per HTTP chunk (one sendmsg: IOV_MAX is 1024)
+
+// `lines` as HTTP chunks — size line, the shared lines themselves, CRLF — gathered by one
+// sendmsg per chunk.  The caller holds s.dmu.  A committer (!blocking) sends what the socket
+// takes at once and leaves the rest in s.backlog for the stream thread; false: the send failed.
+bool send_lines(WatchSlot& s, const std::vector<Line>& lines, bool blocking) {
+  std::vector<struct iovec> iov;
+  for (size_t at = 0; at < lines.size();) {
+    const size_t n = std::min(lines.size() - at, kChunkLines);
+    size_t bytes = 0;
+    for (size_t k = 0; k < n; ++k) bytes += lines[at + k]->size();
+    char hdr[32];
+    const int h = snprintf(hdr, sizeof(hdr), "%zx\r\n", bytes);
+    iov.clear();
+    iov.push_back({hdr, (size_t)h});
+    for (size_t k = 0; k < n; ++k) iov.push_back({const_cast<char*>(lines[at + k]->data()), lines[at + k]->size()});
+    iov.push_back({const_cast<char*>("\r\n"), 2});
+    struct iovec* p = iov.data();
+    int cnt = (int)iov.size();
+    if (s.backlog.empty() && !send_iov(s.fd, p, cnt, blocking ? 0 : MSG_DONTWAIT)) return false;
+    if (cnt > 0) {  // the socket is full (or already was): behind what waits there
+      if (s.backlog.empty()) P.backlogged++;
+      for (int k = 0; k < cnt; ++k) s.backlog.append((const char*)p[k].iov_base, p[k].iov_len);
+    }
+    at += n;
+  }
+  s.last_write_ns.store(mono_ns(), std::memory_order_relaxed);
+  if (!s.backlog.empty()) s.pending.store(true);
+  return true;
+}
+
+enum Drain { DR_NONE, DR_SENT, DR_GONE, DR_DEAD };
+
+// Deliver what the slot's history holds past `seen`.  The caller holds s.dmu with nothing in
+// the backlog, so whichever threads take turns here, the watcher gets its resource's events
+// in resourceVersion order, none missing and none twice — a committer does not send "its"
+// event, it drains (two committers may reach this point in the opposite order of their commits).
+Drain drain(WatchSlot& s, bool blocking) {
+  Bucket& b = *s.bucket;
+  Hist& h = *s.hist;
+  std::vector<Ev> evs;
+  uint64_t oldest_ns = 0;
+  {
+    std::lock_guard<std::mutex> hg(b.hmu);
+    if (h.seq <= s.seen) return DR_NONE;
+    // behind the bounded history: the stream thread answers 410 Gone
+    if (h.hist.empty() || h.hist.front().seq > s.seen + 1) return DR_GONE;
+    const size_t start = h.hist.size() - (size_t)(h.seq - s.seen);
+    P.wakeups++;
+    P.scanned += h.hist.size() - start;
+    // serialise and send outside the history lock (copy the shared event refs first)
+    for (size_t n = start; n < h.hist.size(); ++n) {
+      const Ev& e = h.hist[n];
+      if (s.wants(*e.obj) || (e.old && s.wants(*e.old))) {
+        evs.push_back(e);
+        if (e.t_ns && (!oldest_ns || e.t_ns < oldest_ns)) oldest_ns = e.t_ns;
+      }
+    }
+    s.seen = h.seq;
+  }
+  if (evs.empty()) return DR_NONE;
+  std::vector<Line> lines;
+  lines.reserve(evs.size());
+  for (auto& e : evs) lines.push_back(event_line(*s.res, e.type, *e.obj, *e.cache, s.version));
+  if (!send_lines(s, lines, blocking)) {
+    s.dead.store(true);
+    return DR_DEAD;
+  }
+  (blocking ? P.fallback : P.direct)++;
+  if (g_stall_ms > 0 && oldest_ns) {  // commit -> written to this watcher's socket
+    const double ms = (double)(mono_ns() - oldest_ns) / 1e6;
+    if (ms >= g_stall_ms) {
+      timespec ts;
+      clock_gettime(CLOCK_REALTIME, &ts);
+      fprintf(stderr, "stall-watchdog: watch delivery %.1f ms (%s ns=%s, %zu events, %s) ending at %.6f\n", ms,
+              s.res->plural.c_str(), s.ns.c_str(), lines.size(), blocking ? "stream thread" : "committer",
+              (double)ts.tv_sec + ts.tv_nsec / 1e9);
+    }
+  }
+  return DR_SENT;
+}
+
+// A committing thread at a watcher that wants its event.  It never waits: a slot another
+// thread is delivering to, or one with a backlog, is left to its stream thread (notified; it
+// re-checks the history after every pass, so nothing is lost), the sends do not block, and a
+// failed send only marks the slot — the stream thread owns the fd and ends the watch.
+void deliver_committed(WatchSlot& s) {
+  std::unique_lock<std::mutex> dl(s.dmu, std::try_to_lock);
+  if (!dl.owns_lock()) {
+    s.cv.notify_all();  // the event is published (emit, under hmu): the predicate sees it
+    return;
+  }
+  if (s.fd < 0 || s.dead.load()) return;
+  if (!s.backlog.empty()) {
+    dl.unlock();
+    s.cv.notify_all();
+    return;
+  }
+  const Drain d = drain(s, false);
+  const bool wake = d == DR_GONE || d == DR_DEAD || s.pending.load();
+  dl.unlock();
+  if (wake) wake_stream(s);
 }
 
 void serve_watch(int fd, Res& r, const Path& p, const Request& rq) {
@@ -3008,7 +3436,7 @@ void serve_watch(int fd, Res& r, const Path& p, const Request& rq) {
   auto lr = parse_labels(rq.q.count("labelSelector") ? rq.q.at("labelSelector") : "");
   auto fr = parse_fields(rq.q.count("fieldSelector") ? rq.q.at("fieldSelector") : "");
   std::string ns = r.namespaced ? p.ns : "";
-  // by value: the slot (and this filter) may outlive the stream in a writer's queued wake-up
+  // by value: the slot (and this filter) may outlive the stream in a writer's queued delivery
   auto wants = [ns, lr, fr](const Value& o) {
     if (!ns.empty() && mget(o, "namespace") != ns) return false;
     if (!lr.empty() && !match_labels(lr, o)) return false;
@@ -3017,167 +3445,191 @@ void serve_watch(int fd, Res& r, const Path& p, const Request& rq) {
   };
   std::string head = "HTTP/1.1 200 OK\r\nContent-Type: application/json\r\nTransfer-Encoding: chunked\r\n\r\n";
   if (!write_all(fd, head.data(), head.size())) return;
-  int64_t last_seq;
-  std::vector<std::string> pending;
-  // shared: a writer thread may still hold it (queued wake-up) after this stream ends
+  // shared: a writer thread may still hold it (queued delivery) after this stream ends
   auto slot_ptr = std::make_shared<WatchSlot>();
   WatchSlot& slot = *slot_ptr;
-  Bucket* wb = nullptr;
-  Hist* wh = nullptr;  // the history this watch reads: its namespace's, or the kind's
-  struct Unregister {  // every exit path drops the slot from the bucket's watcher index
-    Bucket*& b;
+  Bucket& b = bucket(r);  // element references of S.data stay valid; buckets are never erased
+  // Every exit path takes the slot off the bucket's watcher index and its fd away, under the
+  // delivery mutex: once this returns no committer writes to the fd, which serve_conn closes
+  // (and the kernel may hand out again).  A committer that still holds the slot finds fd < 0.
+  struct Unregister {
+    Bucket& b;
     const std::string& ns;
-    WatchSlot* s;
+    WatchSlot& s;
+    bool on = false;
     ~Unregister() {
-      if (!b) return;
-      std::lock_guard<std::mutex> hg(b->hmu);
-      auto rg = b->watchers.equal_range(ns);
+      if (!on) return;
+      std::lock_guard<std::mutex> dl(s.dmu);
+      std::lock_guard<std::mutex> hg(b.hmu);
+      s.fd = -1;
+      auto rg = b.watchers.equal_range(ns);
       for (auto it = rg.first; it != rg.second; ++it)
-        if (it->second.get() == s) {
-          b->watchers.erase(it);
+        if (it->second.get() == &s) {
+          b.watchers.erase(it);
+          P.slots--;
           break;
         }
     }
-  } unregister{wb, ns, &slot};
+  } unregister{b, ns, slot};
   slot.wants = wants;
   slot.filtered = !lr.empty() || !fr.empty();
+  slot.bucket = &b;
+  slot.res = &r;
+  slot.version = p.version;
+  slot.ns = ns;
+  slot.fd = fd;
+  slot.last_write_ns.store(mono_ns());
   {
-    Bucket& b = bucket(r);
-    StoreLock g(b);
-    std::lock_guard<std::mutex> hg(b.hmu);
-    wb = &b;
-    wh = ns.empty() ? &b.all : &b.by_ns[ns];
-    b.watchers.emplace(ns, slot_ptr);
-    last_seq = wh->seq;
-    slot.hist = wh;
-    slot.seen = last_seq;
-    if (rv.empty() || rv == "0") {
-      for (auto& kv : b.objs)
-        if (wants(*kv.second)) {
-          Value ev = Value::object();
-          ev["type"] = Value::str("ADDED");
-          ev["object"] = out_obj(r, *kv.second, p.version);
-          pending.push_back(kj::dump(ev) + "\n");
-        }
-    } else {
-      int64_t since = std::stoll(rv);
-      const std::deque<Ev>& hist = wh->hist;
-      // 410 when an event after `since` has fallen off the resource's bounded history
-      if (since < b.dropped_rv) {
-        P.watch_gone++;
-        Value ev = Value::object();
-        ev["type"] = Value::str("ERROR");
-        ev["object"] = status_obj(Gone());
-        pending.push_back(kj::dump(ev) + "\n");
-        last_seq = -1;
+    // the delivery mutex from before the slot is visible until its initial events are out:
+    // committers leave the slot alone meanwhile (and notify; the first pass below catches up)
+    std::lock_guard<std::mutex> dl(slot.dmu);
+    std::vector<Obj> initial;
+    std::vector<Ev> replay;
+    bool gone = false;
+    {
+      StoreLock g(b);
+      std::lock_guard<std::mutex> hg(b.hmu);
+      slot.hist = ns.empty() ? &b.all : &b.by_ns[ns];  // its namespace's history, or the kind's
+      b.watchers.emplace(ns, slot_ptr);
+      P.slots++;
+      unregister.on = true;
+      slot.seen = slot.hist->seq;
+      if (rv.empty() || rv == "0") {
+        for (auto& kv : b.objs)
+          if (wants(*kv.second)) initial.push_back(kv.second);
       } else {
-        for (auto& e : hist)
-          if (e.rv > since && (wants(*e.obj) || (e.old && wants(*e.old)))) pending.push_back(event_line(r, e, p.version));
+        int64_t since = std::stoll(rv);
+        // 410 when an event after `since` has fallen off the resource's bounded history
+        if (since < b.dropped_rv) {
+          gone = true;
+        } else {
+          for (auto& e : slot.hist->hist)
+            if (e.rv > since && (wants(*e.obj) || (e.old && wants(*e.old)))) replay.push_back(e);
+        }
       }
     }
-  }
-  for (auto& l : pending)
-    if (!write_chunk(fd, l)) return;
-  if (last_seq < 0) {
-    write_all(fd, "0\r\n\r\n", 5);
-    return;
+    // serialised outside the store lock: the objects are immutable shared snapshots
+    std::vector<Line> pending;
+    for (auto& o : initial) pending.push_back(make_line(r, "ADDED", *o, p.version));
+    for (auto& e : replay) pending.push_back(event_line(r, e.type, *e.obj, *e.cache, p.version));
+    if (gone) {
+      P.watch_gone++;
+      pending.push_back(error_line(Gone()));
+    }
+    // one chunk per line, as a client that reads the initial state expects to be able to
+    for (auto& l : pending)
+      if (!send_lines(slot, {l}, true)) return;
+    if (gone) {
+      write_all(fd, "0\r\n\r\n", 5);
+      return;
+    }
   }
   auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds((int64_t)(timeout * 1000));
-  auto last_write = std::chrono::steady_clock::now();
+  auto since_write = [&] {
+    return std::chrono::nanoseconds((int64_t)(mono_ns() - slot.last_write_ns.load(std::memory_order_relaxed)));
+  };
+  // what a committer left in the backlog, with blocking sends (the caller holds slot.dmu)
+  auto flush_backlog = [&]() -> bool {
+    if (slot.backlog.empty()) return true;
+    const bool ok = write_all(fd, slot.backlog.data(), slot.backlog.size());
+    std::string().swap(slot.backlog);
+    slot.pending.store(false);
+    slot.last_write_ns.store(mono_ns(), std::memory_order_relaxed);
+    return ok;
+  };
   uint64_t cpu_mark = thread_cpu_ns();
   while (!g_stop) {
+    {
+      Hist& h = *slot.hist;
+      std::unique_lock<std::mutex> lk(b.hmu);
+      // system_clock deadline: libstdc++ maps a steady_clock wait to pthread_cond_clockwait,
+      // which ThreadSanitizer (GCC 11) does not intercept.  The timeout only paces the stream's
+      // own checks (client gone; the watch deadline and the next bookmark cap it) and backs up
+      // the committers' notifications: catch-up scans of a filtered watcher are emit()'s
+      // periodic wake-ups.  At 500 ms, thousands of per-namespace watch threads waking twice a
+      // second were a third of the server's watch CPU at 64 namespaces per rank; a wall-clock
+      // jump is harmless here
+      auto nap = std::chrono::duration_cast<std::chrono::milliseconds>(deadline - std::chrono::steady_clock::now());
+      if (bookmarks)
+        nap = std::min(nap, std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::seconds(10) - since_write()));
+      nap = std::max(std::chrono::milliseconds(1), std::min(nap, std::chrono::milliseconds(5000)));
+      slot.cv.wait_until(lk, std::chrono::system_clock::now() + nap, [&] {
+        return h.seq > slot.seen || slot.pending.load() || slot.dead.load() || g_stop.load();
+      });
+    }
+    // Normally the committers have delivered and there is nothing to do here.  This thread
+    // delivers — with blocking sends — what they left: a backlog, events that arrived while
+    // another thread held the slot, a filtered watcher's catch-up, the 410 Gone.
+    bool wrote = false;
+    Drain d = DR_NONE;
+    {
+      std::lock_guard<std::mutex> dl(slot.dmu);
+      if (slot.dead.load()) return;
+      if (!slot.backlog.empty()) {
+        if (!flush_backlog()) return;
+        wrote = true;
+      }
+      d = drain(slot, true);
+      if (d == DR_DEAD) return;
+      if (d == DR_GONE) {
+        P.watch_gone++;
+        send_lines(slot, {error_line(Gone())}, true);
+      }
+    }
+    if (d == DR_GONE) break;
+    if (d == DR_SENT) wrote = true;
     {  // watch CPU is booked as it accrues (a stream lives for minutes)
       uint64_t now_cpu = thread_cpu_ns();
       P.cpu_ns[C_WATCH] += now_cpu - cpu_mark;
       cpu_mark = now_cpu;
     }
-    std::vector<std::string> lines;
-    uint64_t oldest_ns = 0;
-    bool gone = false;
-    {
-      Bucket& b = *wb;  // element references of S.data stay valid; buckets are never erased
-      Hist& h = *wh;
-      std::unique_lock<std::mutex> lk(b.hmu);
-      // system_clock deadline: libstdc++ maps a steady_clock wait to pthread_cond_clockwait,
-      // which ThreadSanitizer (GCC 11) does not intercept.  The timeout only paces the stream's
-      // own checks (client gone; the watch deadline and the next bookmark cap it): catch-up
-      // scans of a filtered watcher are emit()'s periodic wake-ups.  At 500 ms, thousands of per-namespace watch
-      // threads waking twice a second were a third of the server's watch CPU at 64 namespaces
-      // per rank; a wall-clock jump is harmless here
-      auto nap = std::chrono::duration_cast<std::chrono::milliseconds>(deadline - std::chrono::steady_clock::now());
-      if (bookmarks)
-        nap = std::min(nap, std::chrono::duration_cast<std::chrono::milliseconds>(
-                                last_write + std::chrono::seconds(10) - std::chrono::steady_clock::now()));
-      nap = std::max(std::chrono::milliseconds(1), std::min(nap, std::chrono::milliseconds(5000)));
-      slot.cv.wait_until(lk, std::chrono::system_clock::now() + nap,
-                         [&] { return h.seq > last_seq || g_stop.load(); });
-      if (h.seq > last_seq) {
-        if (!h.hist.empty() && h.hist.front().seq > last_seq + 1) {
-          gone = true;  // the watcher fell behind the bounded history
-        } else {
-          size_t start = h.hist.size() - (size_t)(h.seq - last_seq);
-          P.wakeups++;
-          P.scanned += h.hist.size() - start;
-          // serialise outside the store lock (copy the shared event refs first)
-          std::vector<Ev> evs;
-          for (size_t n = start; n < h.hist.size(); ++n) {
-            const Ev& e = h.hist[n];
-            if (wants(*e.obj) || (e.old && wants(*e.old))) {
-              evs.push_back(e);
-              if (e.t_ns && (!oldest_ns || e.t_ns < oldest_ns)) oldest_ns = e.t_ns;
-            }
-          }
-          last_seq = h.seq;
-          slot.seen = last_seq;
-          lk.unlock();
-          for (auto& e : evs) lines.push_back(event_line(r, e, p.version));
-        }
-      }
-    }
-    if (gone) {
-      P.watch_gone++;
-      Value ev = Value::object();
-      ev["type"] = Value::str("ERROR");
-      ev["object"] = status_obj(Gone());
-      write_chunk(fd, kj::dump(ev) + "\n");
-      break;
-    }
-    if (!lines.empty()) {
-      std::string batch;
-      for (auto& l : lines) batch += l;
-      if (!write_chunk(fd, batch)) return;
-      last_write = std::chrono::steady_clock::now();
-      if (g_stall_ms > 0 && oldest_ns) {  // commit -> written to this watcher's socket
-        const double ms = (double)(mono_ns() - oldest_ns) / 1e6;
-        if (ms >= g_stall_ms) {
-          timespec ts;
-          clock_gettime(CLOCK_REALTIME, &ts);
-          fprintf(stderr, "stall-watchdog: watch delivery %.1f ms (%s ns=%s, %zu events) ending at %.6f\n", ms,
-                  r.plural.c_str(), ns.c_str(), lines.size(), (double)ts.tv_sec + ts.tv_nsec / 1e9);
-        }
-      }
-    }
     auto now = std::chrono::steady_clock::now();
     if (now >= deadline) break;
-    if (socket_closed(fd)) return;
-    if (bookmarks && now - last_write > std::chrono::seconds(10)) {
+    // the client gone: a failed send says so; only a pass that sent nothing has to ask
+    if (!wrote && socket_closed(fd)) return;
+    if (bookmarks && since_write() > std::chrono::seconds(10)) {
       Value bm = Value::object();
       bm["kind"] = Value::str(r.kind);
       bm["apiVersion"] = Value::str(r.api_version(p.version));
       Value m = Value::object();
       {
-        StoreLock g(*wb);  // no commit of this resource in flight: every event below it was sent
+        StoreLock g(b);  // no commit of this resource in flight: every event below it is in the history
         m["resourceVersion"] = Value::str(std::to_string(S.rv.load()));
       }
       bm["metadata"] = m;
       Value ev = Value::object();
       ev["type"] = Value::str("BOOKMARK");
       ev["object"] = bm;
-      if (!write_chunk(fd, kj::dump(ev) + "\n")) return;
-      last_write = now;
+      Line bl = std::make_shared<const std::string>(kj::dump(ev) + "\n");
+      // behind every event up to its resourceVersion: the history is drained first
+      std::lock_guard<std::mutex> dl(slot.dmu);
+      if (slot.dead.load() || !flush_backlog()) return;
+      const Drain bd = drain(slot, true);
+      if (bd == DR_DEAD) return;
+      if (bd == DR_GONE) continue;  // the next pass answers it
+      if (!send_lines(slot, {bl}, true)) return;
     }
   }
+  std::lock_guard<std::mutex> dl(slot.dmu);
+  if (slot.dead.load() || !flush_backlog()) return;
   write_all(fd, "0\r\n\r\n", 5);
+}
+
+// The answer to a write.  The version this thread committed was (or is now) serialised once,
+// as its watch line: the response body is the object inside that line, sent from the shared
+// string.  A write that committed nothing (no-op, dry run) serialises what it returns.
+bool respond_committed(int fd, int code, const Res& r, const Obj& out, const std::string& version, bool keep_alive) {
+  for (auto it = t_emitted.rbegin(); it != t_emitted.rend(); ++it) {
+    if (it->obj != out.get()) continue;
+    Line l;
+    {
+      PhaseTimer pt(PH_DUMP);
+      l = event_line(r, it->type, *out, *it->cache, version);
+    }
+    const size_t pre = line_prefix(it->type);
+    return respond(fd, code, std::string_view(*l).substr(pre, l->size() - pre - 2), keep_alive);
+  }
+  return respond(fd, code, dump_out(r, *out, version), keep_alive);
 }
 
 bool handle(int fd, Request& rq) {
@@ -3251,7 +3703,7 @@ bool handle(int fd, Request& rq) {
   }
   if (rq.method == "GET" && rq.path == "/metrics") {
     int64_t rv = S.rv.load();
-    char buf[1024];  // the longest line below: 14 counters of up to 20 digits and their names
+    char buf[1024];  // the longest line below: 16 counters of up to 20 digits and their names
     snprintf(buf, sizeof(buf),
              "{\"requests\":%llu,\"writes\":%llu,\"webhook_calls\":%llu,\"resourceVersion\":%lld,\"prof\":{",
              (unsigned long long)S.requests.load(), (unsigned long long)S.writes.load(),
@@ -3266,13 +3718,16 @@ bool handle(int fd, Request& rq) {
     snprintf(buf, sizeof(buf),
              "\"lock_wait_ns\":%llu,\"lock_contended\":%llu,\"watch_wakeups\":%llu,\"watch_scanned\":%llu,"
              "\"admit_wall_ns\":%llu,\"trim_ns\":%llu,\"trim_max_ns\":%llu,\"trims\":%llu,"
-             "\"webhook_dials\":%llu,\"webhook_dial_ns\":%llu,\"watch_gone\":%llu,\"process_cpu_ns\":%llu}}",
+             "\"webhook_dials\":%llu,\"webhook_dial_ns\":%llu,\"watch_gone\":%llu,\"watch_direct\":%llu,"
+             "\"watch_fallback\":%llu,\"watch_backlogged\":%llu,\"watch_slots\":%lld,\"process_cpu_ns\":%llu}}",
              (unsigned long long)P.lock_wait_ns.load(), (unsigned long long)P.lock_contended.load(),
              (unsigned long long)P.wakeups.load(), (unsigned long long)P.scanned.load(),
              (unsigned long long)P.admit_wall_ns.load(), (unsigned long long)P.trim_ns.load(),
              (unsigned long long)P.trim_max_ns.load(), (unsigned long long)P.trims.load(),
              (unsigned long long)P.webhook_dials.load(), (unsigned long long)P.webhook_dial_ns.load(),
-             (unsigned long long)P.watch_gone.load(), (unsigned long long)process_cpu_ns());
+             (unsigned long long)P.watch_gone.load(), (unsigned long long)P.direct.load(),
+             (unsigned long long)P.fallback.load(), (unsigned long long)P.backlogged.load(),
+             (long long)P.slots.load(), (unsigned long long)process_cpu_ns());
     out += buf;
     out.pop_back();
     out += ",\"phases\":{";
@@ -3352,8 +3807,7 @@ bool handle(int fd, Request& rq) {
                          "\",\"metadata\":{\"resourceVersion\":\"" + std::to_string(lst.second) + "\"},\"items\":[";
       for (size_t n = 0; n < lst.first.size(); ++n) {
         if (n) body += ',';
-        if (p.version == r.storage) kj::dump(body, *lst.first[n]);
-        else kj::dump(body, out_obj(r, *lst.first[n], p.version));
+        dump_version(body, r, *lst.first[n], p.version);
       }
       body += "]}";
       return respond(fd, 200, body, rq.keep_alive);
@@ -3377,7 +3831,7 @@ bool handle(int fd, Request& rq) {
       if (!body.is_obj()) throw BadRequest("object body required");
       if (!body.get("kind")) body["kind"] = Value::str(r.kind);
       Obj out = do_create(r, p.ns, std::move(body), qget("dryRun") == "All");
-      return respond(fd, 201, dump_out(r, *out, p.version), rq.keep_alive);
+      return respond_committed(fd, 201, r, out, p.version, rq.keep_alive);
     }
     if (rq.method == "PUT" && !p.name.empty()) {
       t_cat = C_UPDATE;
@@ -3387,7 +3841,7 @@ bool handle(int fd, Request& rq) {
         throw BadRequest("the name of the object does not match the name on the URL");
       m["name"] = Value::str(p.name);
       Obj out = do_update(r, p.ns, p.name, std::move(body), p.sub);
-      return respond(fd, 200, dump_out(r, *out, p.version), rq.keep_alive);
+      return respond_committed(fd, 200, r, out, p.version, rq.keep_alive);
     }
     if (rq.method == "PATCH" && !p.name.empty()) {
       t_cat = C_PATCH;
@@ -3399,7 +3853,7 @@ bool handle(int fd, Request& rq) {
         return respond(fd, 415, kj::dump(status_obj({415, "UnsupportedMediaType", "unsupported patch type " + rq.ctype, Value()})),
                        rq.keep_alive);
       Obj out = do_patch(r, p.ns, p.name, body, pt, p.sub);
-      return respond(fd, 200, dump_out(r, *out, p.version), rq.keep_alive);
+      return respond_committed(fd, 200, r, out, p.version, rq.keep_alive);
     }
     if (rq.method == "DELETE" && !p.name.empty()) {
       t_cat = C_DELETE;
@@ -3428,18 +3882,19 @@ void serve_conn(int fd) {
     Request rq;
     if (!read_request(c, rq)) break;
     t_cat = C_OTHER;
-    uint64_t c0 = thread_cpu_ns();
+    t_req_c0 = thread_cpu_ns();
+    t_counted = false;
+    t_deliver_ns = 0;
+    t_emitted.clear();
     t_aud.on = false;
     bool more = handle(fd, rq);
+    if (!t_wake.empty()) flush_wakes();  // the response is out: now its events (g_respond_first)
     if (t_aud.on) {
       audit_write(t_aud, rq.target, rq.user_agent, rq.body, "ResponseComplete");
       t_aud.on = false;
       t_aud.resp.clear();
     }
-    if (t_cat != C_WATCH) {  // a watch books its own CPU as it goes
-      P.cpu_ns[t_cat] += thread_cpu_ns() - c0;
-      P.calls[t_cat]++;
-    }
+    book_request();  // what came after the response was booked (respond): its send
     if (!more) break;
     if (!rq.keep_alive) break;
   }
@@ -3551,6 +4006,7 @@ int main(int argc, char** argv) {
   // a stall of the whole process (scheduling, the address-space lock, an allocator lock)
   // shows up here, a stall of one request path does not
   if (const char* e = std::getenv("ODH_STALL_WATCHDOG_MS")) g_stall_ms = std::atoi(e);
+  if (const char* e = std::getenv("ODH_APISERVER_WATCHERS_FIRST")) g_respond_first = std::atoi(e) == 0;
   if (g_stall_ms > 0)
     std::thread([] {
       while (!g_stop) {

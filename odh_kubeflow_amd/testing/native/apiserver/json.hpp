@@ -369,6 +369,32 @@ inline void dump(std::string& out, const Value& v) {
   }
 }
 
+// The object `v` with its string member `key` written as `val` (appended when `v` has no such
+// member): what dump() gives for a copy of `v` with v[key] = val, without the copy.
+inline void dump_with(std::string& out, const Value& v, std::string_view key, const std::string& val) {
+  if (v.t != T::Object) return dump(out, v);
+  out += '{';
+  bool found = false;
+  for (size_t n = 0; n < v.obj.size(); ++n) {
+    if (n) out += ',';
+    escape(out, v.obj[n].k);
+    out += ':';
+    if (v.obj[n].k == key) {
+      found = true;
+      escape(out, val);
+    } else {
+      dump(out, v.obj[n].v);
+    }
+  }
+  if (!found) {
+    if (!v.obj.empty()) out += ',';
+    escape(out, std::string(key));
+    out += ':';
+    escape(out, val);
+  }
+  out += '}';
+}
+
 inline std::string dump(const Value& v) {
   std::string s;
   s.reserve(512);
