@@ -24,8 +24,9 @@ pods that request GPUs also get the AMD node-labeller selector and the
 gets a memory-backed one of that size per GPU: PyTorch DataLoader workers and RCCL's
 intra-node transport live there, and the container default (64 MiB) breaks both.  The
 ``amd.com/shm-size`` annotation overrides the size (``0`` turns it off).  With
-``amd.com/gpu-probe: "true"`` on the Notebook (or ``GPU_STARTUP_PROBE=true`` for every GPU
-notebook) the pod gets the ``amd-gpu-probe`` init container: the MI355X start-up probe
+``amd.com/gpu-probe: "true"`` on the Notebook (a comma list of ``true``, ``rccl``, ``mx``; or
+``GPU_STARTUP_PROBE=true`` for every GPU notebook) the pod gets the ``amd-gpu-probe`` init
+container: the MI355X start-up probe
 (``odh-gpu-probe``, ``GPU_PROBE_IMAGE``) on the GPUs the device plugin gives it, before the
 notebook container starts.
 
@@ -174,37 +175,61 @@ GPU_PROBE_ANNOTATION = "amd.com/gpu-probe"
 GPU_PROBE_CONTAINER = "amd-gpu-probe"
 DEFAULT_GPU_PROBE_IMAGE = "quay.io/opendatahub/odh-kubeflow-amd-gpu-probe:main"  # manifests pin the release
 GPU_PROBE_TIMEOUT_MS = "30000"
-GPU_PROBE_RCCL_MIB = "64"  # all-reduce size of the RCCL step (annotation value "rccl")
+GPU_PROBE_RCCL_MIB = "64"  # all-reduce size of the RCCL step (annotation token "rccl")
+GPU_PROBE_MX_FORMATS = "fp8,fp4"  # block-scaled formats of the MX step (annotation token "mx")
+
+
+GPU_PROBE_TOKENS = ("true", "rccl", "mx", "false")
+
+
+def gpu_probe_tokens(nb: dict) -> frozenset:
+    """The ``amd.com/gpu-probe`` annotation as a set of tokens.  It is a comma list of ``true``,
+    ``rccl``, ``mx`` and ``false``: ``rccl`` and ``mx`` each turn the probe on and add their step,
+    so ``"rccl,mx"`` runs both.  A value with an unknown token, or with ``false`` next to another
+    token, is ignored as a whole (the empty set), like an unknown value."""
+    v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
+    tokens = frozenset(t.strip() for t in v.split(",")) if v else frozenset()
+    if not tokens <= frozenset(GPU_PROBE_TOKENS) or ("false" in tokens and len(tokens) > 1):
+        return frozenset()
+    return tokens
 
 
 def gpu_probe_enabled(nb: dict, pod_spec: dict, env: Mapping[str, str] = os.environ) -> bool:
     """The MI355X start-up probe runs for notebooks that request ``amd.com/gpu`` when the
-    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``), or when the operator turned
-    it on for every GPU notebook (``GPU_STARTUP_PROBE=true``) and the Notebook does not say
-    ``"false"``.  Off by default (never on the reconcile path, opt-in)."""
+    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, or a comma list of
+    them), or when the operator turned it on for every GPU notebook (``GPU_STARTUP_PROBE=true``)
+    and the Notebook does not say ``"false"``.  Off by default (never on the
+    reconcile path, opt-in)."""
     if gpu_request(pod_spec) <= 0:
         return False
-    v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
-    if v in ("true", "rccl", "false"):
-        return v != "false"
+    tokens = gpu_probe_tokens(nb)
+    if tokens:
+        return "false" not in tokens
     return env.get("GPU_STARTUP_PROBE", "false") == "true"
 
 
 def gpu_probe_rccl(nb: dict, ngpu: int, env: Mapping[str, str] = os.environ) -> bool:
     """Whether the probe also runs its RCCL all-reduce over the pod's GPUs (SURVEY §7.0.4's
-    collective readiness check): ``amd.com/gpu-probe: "rccl"``, or ``GPU_PROBE_RCCL=true`` for
+    collective readiness check): ``rccl`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_RCCL=true`` for
     every probed notebook with 2+ GPUs (a single GPU has nothing to all-reduce with)."""
-    v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
-    return v == "rccl" or (ngpu >= 2 and env.get("GPU_PROBE_RCCL", "false") == "true")
+    return "rccl" in gpu_probe_tokens(nb) or (ngpu >= 2 and env.get("GPU_PROBE_RCCL", "false") == "true")
 
 
-def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False) -> dict:
+def gpu_probe_mx(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
+    """Whether the probe also checks the block-scaled FP8 / MXFP4 matrix cores (``--mx fp8,fp4``):
+    ``mx`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_MX=true`` for every probed notebook."""
+    return "mx" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_MX", "false") == "true"
+
+
+def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False,
+                             mx: bool = False) -> dict:
     """Init container that proves the pod's GPUs healthy before the notebook starts.
 
     ``odh-gpu-probe`` (``ops/csrc/probe_cli.cpp``, torch-free) runs the bf16 MFMA GEMM checked
     in registers and the HBM3E pattern sweep on every GPU the device plugin gives the pod, and
     with 2+ GPUs reads the xGMI ring between them (``rccl``: plus an RCCL all-reduce over all
-    of them, ``--rccl-mib``); non-zero exit keeps the pod in Init, and its
+    of them, ``--rccl-mib``; ``mx``: plus the FP8 and MXFP4 block-scaled GEMMs checked the same
+    way, ``--mx fp8,fp4``); non-zero exit keeps the pod in Init, and its
     JSON verdict is the container's termination message.  It asks for the same
     ``amd.com/gpu`` count as the notebook: the kubelet device manager hands an init
     container's devices on to the app containers, so the GPUs probed are the GPUs the
@@ -213,6 +238,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
     args = ["--json", "/dev/termination-log", "--timeout-ms", env.get("GPU_PROBE_TIMEOUT_MS") or GPU_PROBE_TIMEOUT_MS]
     if rccl:
         args += ["--rccl-mib", GPU_PROBE_RCCL_MIB]
+    if mx:
+        args += ["--mx", GPU_PROBE_MX_FORMATS]
     return {
         "name": GPU_PROBE_CONTAINER,
         "image": env.get("GPU_PROBE_IMAGE") or DEFAULT_GPU_PROBE_IMAGE,
@@ -233,7 +260,7 @@ def _gpu_probe(nb: dict, pod_spec: dict, env: Mapping[str, str]) -> None:
         return  # the user brought their own
     n = gpu_request(pod_spec)
     # before any init container that uses the GPU
-    inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env)))
+    inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env), mx=gpu_probe_mx(nb, env)))
 
 
 def generate_statefulset(nb: dict, is_generate_name: bool, env: Mapping[str, str] = os.environ) -> dict:

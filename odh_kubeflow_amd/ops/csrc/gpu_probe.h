@@ -26,6 +26,10 @@ enum {
   ODH_SLOT_CLI_RCCL_ERR = 22,      // u64: mismatches in this device's RCCL all-reduce result
   ODH_SLOT_GRAPH_GEMM_SPAN = 20,   // 2 × u64: ~(earliest begin), latest end (wall_clock64 ticks)
   ODH_SLOT_GRAPH_SWEEP_SPAN = 24,  // 2 × u64: the same for the HBM write + check
+  // operand formats of the block-scaled (MX) kernels: the hardware's format codes
+  ODH_MX_FP8 = 0,  // OCP e4m3fn, one byte per element
+  ODH_MX_FP4 = 4,  // e2m1, two elements per byte (even k in the low nibble)
+  ODH_MX_CLASSES = 315,  // floats in the table of expected values: (i mod 15, j mod 21)
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -69,6 +73,16 @@ int odh_hbm_check_variant(const void* buf, size_t bytes, uint32_t seed, unsigned
 int odh_const_check(const void* buf, size_t bytes, uint32_t expect, unsigned long long* err, hipStream_t stream);
 int odh_peer_enable(int dev, int peer);
 int odh_busy(float* out, int blocks, int iters, hipStream_t stream);
+// Block-scaled FP8 / MXFP4 (fmt: ODH_MX_*): A [M][K] and Bt [N][K] codes, sA / sBt [rows][K/32] E8M0
+// bytes (4-byte aligned), M and N multiples of 256, K of 64 (FP8) or 128 (FP4); table: ODH_MX_CLASSES floats
+int odh_mx_zero_classes(int K);  // host only: classes expecting 0 at this K (-1: K not a multiple of 128)
+int odh_mx_fill(int fmt, void* A, void* Bt, void* sA, void* sBt, float* table, int M, int N, int K,
+                hipStream_t stream);
+int odh_mx_gemm(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt, float* C, int M, int N, int K,
+                hipStream_t stream);
+int odh_mx_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt,
+                             const float* table, int M, int N, int K, int* tile_xcd, int* counters,
+                             hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

@@ -29,6 +29,9 @@
 //  * odh_probe_graph_create / _launch / _destroy — the probe captured as one hipGraph.
 //  * odh_gemm_bf16_256_variant, odh_probe_gemm_verify_2buf / _deep, odh_hbm_write_variant,
 //    odh_hbm_check_variant — A/B entry points (microbenchmarks, kernel numerics tests).
+//  * odh_mx_fill / odh_mx_gemm / odh_mx_probe_gemm_verify — the same exact check on the
+//    block-scaled FP8 / MXFP4 path (v_mfma_scale_f32_32x32x64_f8f6f4; gpu_probe_mx.h), and
+//    odh_mx_zero_classes, the host-side guard against a K at which that check is blind.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -572,6 +575,8 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
   }
   if (ts && lane == 0) ts_end(ts);
 }
+
+#include "gpu_probe_mx.h"  // the FP8 / MXFP4 block-scaled kernels, on the tile helpers above
 
 __device__ __forceinline__ uint16_t small_int_bf16(int v) {
   // exact for |v| < 256: take the high half of the f32 bit pattern
@@ -1123,6 +1128,66 @@ int odh_const_check(const void* buf, size_t bytes, uint32_t expect, unsigned lon
   const size_t n = bytes / 16;
   if (n == 0 || bytes % 16) return (int)hipErrorInvalidValue;
   const_check_kernel<<<grid_for(n, 1024), 256, 0, stream>>>((const u32x4*)buf, n, expect, err);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ FP8 / MXFP4 (gpu_probe_mx.h)
+
+// host only (no HIP call): how many of the 315 (i mod 15, j mod 21) classes expect 0 at this K,
+// where the check cannot tell a right product from an all-zero one; -1 for a K that is not a
+// positive multiple of 128
+int odh_mx_zero_classes(int K) {
+  if (K <= 0 || K % 128) return -1;
+  int zeros = 0;
+  for (int t = 0; t < MX_CLASSES; ++t) zeros += mx_expect4(t / MX_COLS, t % MX_COLS, K) == 0;
+  return zeros;
+}
+
+// the probe operands encoded for fmt, their scales, and the 15 × 21 table of expected values
+int odh_mx_fill(int fmt, void* A, void* Bt, void* sA, void* sBt, float* table, int M, int N, int K,
+                hipStream_t stream) {
+  if (!mx_ok(fmt, M, N, K) || !A || !Bt || !sA || !sBt || !table) return (int)hipErrorInvalidValue;
+  const size_t n = ((size_t)M + N) * (size_t)(K / (fmt == ODH_MX_FP4 ? 2 : 1)) + ((size_t)M + N) * (size_t)(K / 32);
+  mx_fill_kernel<<<grid_for(n, 256), 256, 0, stream>>>(fmt, (uint8_t*)A, (uint8_t*)Bt, (uint8_t*)sA, (uint8_t*)sBt, M,
+                                                      N, K);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  mx_table_kernel<<<MX_CLASSES, 64, 0, stream>>>(table, K);
+  return (int)hipGetLastError();
+}
+
+// C[M][N] = (A ∘ sA) · (Bt ∘ sBt)ᵀ in fp32 for any codes and scales
+int odh_mx_gemm(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt, float* C, int M, int N, int K,
+                hipStream_t stream) {
+  if (!mx_ok(fmt, M, N, K) || !mx_aligned(A, Bt, sA, sBt) || !C) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
+  if (fmt == ODH_MX_FP4)
+    mx_gemm256_kernel<ODH_MX_FP4, false><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, C, nullptr, N, K, nullptr, nullptr,
+        nullptr, nullptr);
+  else
+    mx_gemm256_kernel<ODH_MX_FP8, false><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, C, nullptr, N, K, nullptr, nullptr,
+        nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+// the same tiles with the check against odh_mx_fill's table fused into the epilogue; counters is
+// a counter block of this format's own (ODH_SLOT_XCD_BLOCKS, ODH_SLOT_ERR_XCD, ODH_SLOT_GEMM_ERR)
+int odh_mx_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt,
+                             const float* table, int M, int N, int K, int* tile_xcd, int* counters,
+                             hipStream_t stream) {
+  if (!mx_ok(fmt, M, N, K) || !mx_aligned(A, Bt, sA, sBt) || !table || !counters) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
+  unsigned* c = (unsigned*)counters;
+  if (fmt == ODH_MX_FP4)
+    mx_gemm256_kernel<ODH_MX_FP4, true><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, nullptr, table, N, K, tile_xcd,
+        counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  else
+    mx_gemm256_kernel<ODH_MX_FP8, true><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, nullptr, table, N, K, tile_xcd,
+        counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

@@ -17,7 +17,12 @@
 //   4. with --rccl-mib N (the `amd.com/gpu-probe: "rccl"` notebooks), an RCCL all-reduce over
 //      all of them in this one process (ncclCommInitAll; librccl is dlopen'ed only then — it
 //      is 570 MB), every element of every device's result checked on its GPU: the
-//      collective library and its xGMI transport ready for the notebook's torch.distributed.
+//      collective library and its xGMI transport ready for the notebook's torch.distributed;
+//   5. with --mx fp8,fp4 (the `amd.com/gpu-probe: "mx"` notebooks), after the HBM sweep and on
+//      its stream, per format: the probe operands re-encoded as FP8 / MXFP4 codes with E8M0
+//      block scales into the bf16 operands' buffers (odh_mx_fill), then the block-scaled GEMM
+//      (v_mfma_scale_f32_32x32x64_f8f6f4) checked in registers against a 15 × 21 table
+//      (odh_mx_probe_gemm_verify): the data path a quantised model runs on.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -33,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is dlopen'ed (rccl_allreduce)
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -63,7 +69,8 @@ struct Options {
   size_t rccl_bytes = 0;  // 0: no RCCL step
   long timeout_ms = 30000;
   std::string json_path;  // "" = default; "-" = stdout only
-  std::string fault;      // test hook: gemm | hbm | xgmi | rccl
+  std::string fault;      // test hook: gemm | hbm | xgmi | rccl | mx
+  std::vector<int> mx;    // --mx: ODH_MX_* formats to check, in the order given
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
   // 1 = one stream, 2 = the HBM sweep overlapping the GEMM on a second stream.  Each stream is
@@ -88,13 +95,22 @@ struct Dev {
   float gemm_ms = 0, hbm_ms = 0, link_ms = 0, rccl_ms = 0;
   double malloc_ms = 0, streams_ms = 0, events_ms = 0, first_op_ms = 0;  // host-side set-up, step by step
   int link_source = -1;
+  // --mx: scales and table behind the counters, one counter block and event pair per format
+  void *mx_sa = nullptr, *mx_sbt = nullptr;
+  float* mx_table = nullptr;
+  int* mx_counters = nullptr;
+  int mx_host[2][ODH_NCOUNT] = {};
+  hipEvent_t e_mx0[2] = {}, e_mx1[2] = {};
+  float mx_ms[2] = {};
   std::string error;
 };
+
+const char* mx_name(int fmt) { return fmt == ODH_MX_FP4 ? "fp4" : "fp8"; }
 
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
-               "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl] [--quiet]\n",
+               "[--mx fp8,fp4] [--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx] [--quiet]\n",
                argv0);
   return 64;
 }
@@ -128,7 +144,17 @@ bool parse(int argc, char** argv, Options& o) {
       if (o.streams < 0 || o.streams > 2) return false;
     } else if (a == "--inject-fault") {
       o.fault = v;
-      if (v != "gemm" && v != "hbm" && v != "xgmi" && v != "rccl") return false;
+      if (v != "gemm" && v != "hbm" && v != "xgmi" && v != "rccl" && v != "mx") return false;
+    } else if (a == "--mx") {
+      // a comma list of formats, each at most once
+      for (size_t at = 0; at <= v.size();) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string name = v.substr(at, comma - at);
+        const int fmt = name == "fp8" ? ODH_MX_FP8 : name == "fp4" ? ODH_MX_FP4 : -1;
+        if (fmt < 0 || std::find(o.mx.begin(), o.mx.end(), fmt) != o.mx.end()) return false;
+        o.mx.push_back(fmt);
+        at = comma + 1;
+      }
     } else if (a == "--quiet") {
       o.quiet = true;
     } else {
@@ -139,6 +165,10 @@ bool parse(int argc, char** argv, Options& o) {
   // the probe operands sum to zero over their period of 35 in k: at K % 35 == 0 the expected
   // product is 0 everywhere and matrix cores that return zeros would pass, so K is refused
   // the all-reduce's send and receive buffers are the two halves of the HBM buffer
+  // --mx: one K for both formats (128 = one FP4 stage), and none of the 315 classes of the MX
+  // operands may expect 0 at it (odh_mx_zero_classes: host arithmetic, before any HIP call)
+  if (!o.mx.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
+  if (o.fault == "mx" && o.mx.empty()) return false;
   return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 && o.K % 35 != 0 &&
          o.hbm_bytes >= (1u << 20) && o.timeout_ms > 0 && 2 * o.rccl_bytes <= o.hbm_bytes &&
          (o.fault != "rccl" || o.rccl_bytes > 0);
@@ -201,7 +231,11 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t na = align_up((size_t)o.M * o.K * 2), nb = align_up((size_t)o.N * o.K * 2);
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + align_up(sizeof(int) * ODH_NCOUNT)));
+  // --mx adds a counter block per format behind the first, the scales of both operands and the table
+  const size_t nmx = o.mx.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nmx));
+  const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
+  const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -209,6 +243,12 @@ bool setup_alloc(Dev& d, const Options& o) {
   d.hbm = p + na + nb;
   d.tile_xcd = (int*)(p + na + nb + nh);
   d.counters = (int*)(p + na + nb + nh + nt);
+  if (nmx) {
+    d.mx_counters = d.counters + ODH_NCOUNT;
+    d.mx_sa = p + na + nb + nh + nt + nc;
+    d.mx_sbt = p + na + nb + nh + nt + nc + nsa;
+    d.mx_table = (float*)(p + na + nb + nh + nt + nc + nsa + nsb);
+  }
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -217,11 +257,15 @@ bool setup_alloc(Dev& d, const Options& o) {
   t0 = Clock::now();
   for (hipEvent_t* e : {&d.e0, &d.e_gemm, &d.e_h0, &d.e_h1, &d.e_link0, &d.e_link1, &d.e_r0, &d.e_r1})
     HIP_TRY(hipEventCreate(e));
+  for (size_t f = 0; f < nmx; ++f) {
+    HIP_TRY(hipEventCreate(&d.e_mx0[f]));
+    HIP_TRY(hipEventCreate(&d.e_mx1[f]));
+  }
   d.events_ms = ms_since(t0);
   // the first operation on the stream: on the null stream it creates the hardware queue, here
   // while the other thread is still loading the code object
   t0 = Clock::now();
-  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT, d.sg));
+  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nmx), d.sg));
   d.first_op_ms = ms_since(t0);
   return true;
 }
@@ -277,6 +321,32 @@ bool finish(Dev& d) {
   return true;
 }
 
+// format f of --mx on the sweep's stream, after the sweep: the operands re-encoded into the bf16
+// operands' buffers (that GEMM is done, and the codes are no larger), then the fused check
+bool mx_launch(Dev& d, const Options& o, size_t f) {
+  const int fmt = o.mx[f];
+  int* counters = d.mx_counters + f * ODH_NCOUNT;
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_mx_fill(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, d.sh));
+  if (o.fault == "mx") {
+    // A[0][0] becomes +3 (FP4: A[0][1], the high nibble, is 0): row 0 of C is wrong wherever Bt[j][0] != 0
+    HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_MX_FP4 ? 0x05 : 0x44, 1, d.sh));
+  }
+  HIP_TRY(hipEventRecord(d.e_mx0[f], d.sh));
+  HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, counters,
+                                   d.sh));
+  HIP_TRY(hipEventRecord(d.e_mx1[f], d.sh));
+  HIP_TRY(hipMemcpyAsync(d.mx_host[f], counters, sizeof d.mx_host[f], hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+bool mx_finish(Dev& d, size_t f) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(hipStreamSynchronize(d.sh));
+  HIP_TRY(hipEventElapsedTime(&d.mx_ms[f], d.e_mx0[f], d.e_mx1[f]));
+  return true;
+}
+
 // reader d checks source s's freshly written pattern over xGMI
 bool link_check(Dev& d, const Dev& s, const Options& o) {
   HIP_TRY(odh_peer_enable(d.index, s.index));
@@ -304,6 +374,10 @@ void release(Dev& d) {
   if (d.block) (void)hipFree(d.block);
   for (hipEvent_t e : {d.e0, d.e_gemm, d.e_h0, d.e_h1, d.e_link0, d.e_link1, d.e_r0, d.e_r1})
     if (e) (void)hipEventDestroy(e);
+  for (int f = 0; f < 2; ++f) {
+    if (d.e_mx0[f]) (void)hipEventDestroy(d.e_mx0[f]);
+    if (d.e_mx1[f]) (void)hipEventDestroy(d.e_mx1[f]);
+  }
   if (d.sh && d.sh != d.sg) (void)hipStreamDestroy(d.sh);
   if (d.sg) (void)hipStreamDestroy(d.sg);
 }
@@ -528,6 +602,18 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
+  // --mx: one format at a time over every device, so each format has a host time of its own
+  double mx_host_ms[2] = {};
+  const auto t_mx0 = Clock::now();
+  for (size_t f = 0; f < o.mx.size(); ++f) {
+    const auto t0 = Clock::now();
+    for (Dev& d : devs)
+      if (!mx_launch(d, o, f)) return fail_all(d);
+    for (Dev& d : devs)
+      if (!mx_finish(d, f)) return fail_all(d);
+    mx_host_ms[f] = ms_since(t0);
+  }
+  const double mx_total_ms = ms_since(t_mx0);
   // xGMI ring: device r reads the pattern device r-1 wrote (2 GPUs: each reads the other)
   const auto t_link0 = Clock::now();
   if (ndev >= 2) {
@@ -623,13 +709,49 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                   ndev > 1 ? algbw * 2.0 * (ndev - 1) / ndev : algbw);
     rccl = b;
   }
+  // per format, whatever the device count: total mismatches, the slowest device's kernel time
+  std::string mx;
+  for (size_t f = 0; f < o.mx.size(); ++f) {
+    uint64_t errs = 0;
+    float slowest = 0;
+    bool fok = true;
+    for (Dev& d : devs) {
+      const int* h = d.mx_host[f];
+      long blocks = 0;
+      std::string where;
+      for (int x = 0; x < ODH_N_XCD; ++x) {
+        blocks += h[ODH_SLOT_XCD_BLOCKS + x];
+        if (h[ODH_SLOT_ERR_XCD + x]) where += (where.empty() ? "" : ",") + std::to_string(x);
+      }
+      const uint32_t e = (uint32_t)h[ODH_SLOT_GEMM_ERR];
+      errs += e;
+      slowest = d.mx_ms[f] > slowest ? d.mx_ms[f] : slowest;
+      if (e == 0 && blocks == tiles) continue;
+      fok = false;
+      if (first_err.empty()) {
+        char b[200];
+        std::snprintf(b, sizeof b, "GPU %d: %s: %u MX GEMM mismatches on XCD %s, %ld/%d tiles", d.index, mx_name(o.mx[f]),
+                      e, where.empty() ? "-" : where.c_str(), blocks, tiles);
+        first_err = b;
+      }
+    }
+    ok = ok && fok;
+    char b[128];
+    std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"tflops\":%.1f,\"host_ms\":%.3f}",
+                  f ? "," : ",\"mx\":{", mx_name(o.mx[f]), fok ? "true" : "false", (unsigned long long)errs, slowest,
+                  slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, mx_host_ms[f]);
+    mx += b;
+  }
+  if (!mx.empty()) mx += "}";
   for (Dev& d : devs) release(d);
-  char tail[448];
+  char mx_timing[48] = "";
+  if (!o.mx.empty()) std::snprintf(mx_timing, sizeof mx_timing, "\"mx\":%.3f,", mx_total_ms);
+  char tail[512];
   std::snprintf(tail, sizeof tail,
                 ",\"timings_ms\":{\"exec\":%.3f,\"hip_init\":%.3f,\"alloc_fill\":%.3f,\"alloc\":%.3f,"
-                "\"code_load\":%.3f,\"fill\":%.3f,\"probe\":%.3f,\"xgmi\":%.3f,\"rccl\":%.3f,\"total\":%.3f}}",
+                "\"code_load\":%.3f,\"fill\":%.3f,\"probe\":%.3f,\"xgmi\":%.3f,\"rccl\":%.3f,%s\"total\":%.3f}}",
                 t_exec, t_init, t_alloc - t_init, t_alloc_only - t_init, t_preload - t_init, t_alloc - t_malloc, probe_ms,
-                link_ms, rr.load_ms + rr.init_ms + rr.wall_ms, ms_since(t_start));
+                link_ms, rr.load_ms + rr.init_ms + rr.wall_ms, mx_timing, ms_since(t_start));
   char setup[192];
   std::snprintf(setup, sizeof setup,
                 ",\"setup_ms\":{\"malloc\":%.3f,\"streams\":%.3f,\"events\":%.3f,\"first_op\":%.3f,\"n_streams\":%d}",
@@ -638,6 +760,6 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                      ",\"shape\":[" + std::to_string(o.M) + "," + std::to_string(o.N) + "," + std::to_string(o.K) +
                      "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
                      (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
-                     ",\"links\":" + links + rccl + setup + tail;
+                     ",\"links\":" + links + rccl + mx + setup + tail;
   return done(ok ? 0 : 1, json);
 }

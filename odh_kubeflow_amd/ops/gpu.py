@@ -14,6 +14,9 @@
   since events cannot split a graph launch.  Reports matrix-core TFLOP/s, HBM GB/s,
   mismatches (attributed to the XCD that computed them) and how many of the 8 XCDs ran
   workgroups.
+* :func:`mx_fill`, :func:`mx_gemm`, :func:`mx_probe` — the block-scaled FP8 / MXFP4 path of the
+  matrix cores (``v_mfma_scale_f32_32x32x64_f8f6f4``) on uint8 code tensors: the same exact
+  in-register check, against a 15 × 21 table (``odh-gpu-probe --mx``).
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
@@ -56,6 +59,12 @@ ODH_SLOT_CLI_XGMI_ERR = 20  # u64 (odh-gpu-probe only)
 ODH_SLOT_CLI_RCCL_ERR = 22  # u64 (odh-gpu-probe only)
 ODH_SLOT_GRAPH_GEMM_SPAN = 20  # 2 × u64: ~begin, end (odh_probe_graph_create)
 ODH_SLOT_GRAPH_SWEEP_SPAN = 24  # 2 × u64
+# operand formats of the block-scaled (MX) kernels: the hardware's format codes
+ODH_MX_FP8 = 0  # OCP e4m3fn, one byte per element
+ODH_MX_FP4 = 4  # e2m1, two elements per byte (even k in the low nibble)
+ODH_MX_CLASSES = 315  # floats in the table of expected values
+MX_FORMATS = {"fp8": ODH_MX_FP8, "fp4": ODH_MX_FP4}
+MX_TABLE = (15, 21)  # expected values of the MX probe operands, by (i mod 15, j mod 21)
 
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -83,6 +92,11 @@ SIGNATURES = {
     "odh_probe_gemm_verify_deep": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "odh_hbm_write_variant": (_i, [_vp, _sz, _u32, _i, _i, _vp]),
     "odh_hbm_check_variant": (_i, [_vp, _sz, _u32, _vp, _i, _i, _vp]),
+    # block-scaled FP8 / MXFP4 (csrc/gpu_probe_mx.h)
+    "odh_mx_zero_classes": (_i, [_i]),
+    "odh_mx_fill": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_mx_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_mx_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -205,6 +219,125 @@ def gemm_bf16(a, bt, out=None, tile_xcd=None, xcd_blocks=None, tile: Optional[in
                              tile_xcd.data_ptr() if tile_xcd is not None else None,
                              xcd_blocks.data_ptr() if xcd_blocks is not None else None, _stream_ptr(a.device)))
     return out
+
+
+def _mx_format(fmt) -> int:
+    code = MX_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in MX_FORMATS.values():
+        raise ValueError(f"MX format must be one of {sorted(MX_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def mx_shape_ok(fmt, m: int, n: int, k: int) -> bool:
+    """256² output tiles, and K in stages of 64 bytes per row: 64 FP8 or 128 FP4 elements."""
+    bk = 128 if _mx_format(fmt) == ODH_MX_FP4 else 64
+    return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
+
+
+def mx_zero_classes(k: int) -> int:
+    """How many of the 315 ``(i mod 15, j mod 21)`` classes of the MX probe operands expect 0 at
+    this K (-1: K is no positive multiple of 128).  Host arithmetic only."""
+    return load_library().odh_mx_zero_classes(k)
+
+
+def _mx_operands(fmt, a, bt, sa, sbt):
+    """Checks of the MX entry points, before launch: uint8, one GPU, contiguous, and the public
+    layout (A ``[M, K/epb]``, Bt ``[N, K/epb]`` codes, scales ``[rows, K/32]``).  Returns M, N, K."""
+    import torch
+
+    code = _mx_format(fmt)
+    ts = (a, bt, sa, sbt)
+    if any(t.dtype != torch.uint8 for t in ts):
+        raise TypeError("MX operands and scales are uint8 codes")
+    if any(t.dim() != 2 for t in ts):
+        raise ValueError("MX operands and scales are 2-D")
+    if not all(t.is_cuda and t.device == a.device for t in ts):
+        raise ValueError("operands and scales must live on the same GPU")
+    if not all(t.is_contiguous() for t in ts):
+        raise ValueError("operands and scales must be contiguous")
+    epb = 2 if code == ODH_MX_FP4 else 1
+    m, n, k = a.shape[0], bt.shape[0], a.shape[1] * epb
+    if bt.shape[1] != a.shape[1] or not mx_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {64 * epb}; got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    if tuple(sa.shape) != (m, k // 32) or tuple(sbt.shape) != (n, k // 32):
+        raise ValueError(f"scales must be [{m},{k // 32}] and [{n},{k // 32}]; "
+                         f"got {tuple(sa.shape)} {tuple(sbt.shape)}")
+    return code, m, n, k
+
+
+def mx_fill(fmt, a, bt, sa, sbt, table) -> None:
+    """The probe operands encoded for ``fmt`` (``"fp8"`` / ``"fp4"``), their E8M0 block scales and
+    the 15 × 21 fp32 table of expected values, written into the given tensors."""
+    import torch
+
+    code, m, n, k = _mx_operands(fmt, a, bt, sa, sbt)
+    if (table.dtype != torch.float32 or tuple(table.shape) != MX_TABLE or not table.is_contiguous()
+            or table.device != a.device):
+        raise ValueError("table must be a contiguous fp32 [15,21] tensor on the operands' GPU")
+    _check(load_library().odh_mx_fill(code, a.data_ptr(), bt.data_ptr(), sa.data_ptr(), sbt.data_ptr(),
+                                      table.data_ptr(), m, n, k, _stream_ptr(a.device)))
+
+
+def mx_gemm(fmt, a, bt, sa, sbt, out=None):
+    """``C[M,N] = (A ∘ sA) · (Bt ∘ sBt)ᵀ`` in fp32 on the block-scaled matrix cores
+    (``v_mfma_scale_f32_32x32x64_f8f6f4``): uint8 codes, one E8M0 scale per 32 k of a row."""
+    import torch
+
+    code, m, n, k = _mx_operands(fmt, a, bt, sa, sbt)
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != (m, n) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a.device:
+        raise ValueError("out must be a contiguous fp32 [M,N] tensor on the operands' GPU")
+    _check(load_library().odh_mx_gemm(code, a.data_ptr(), bt.data_ptr(), sa.data_ptr(), sbt.data_ptr(),
+                                      out.data_ptr(), m, n, k, _stream_ptr(a.device)))
+    return out
+
+
+def mx_verify(fmt, a, bt, sa, sbt, table) -> dict:
+    """The fused check of the given operands against ``table`` on a fresh counter block; the
+    kernel's time is taken with events around its one launch."""
+    import torch
+
+    code, m, n, k = _mx_operands(fmt, a, bt, sa, sbt)
+    dev = a.device
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
+        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load_library().odh_mx_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), sa.data_ptr(),
+                                                       sbt.data_ptr(), table.data_ptr(), m, n, k, tile_xcd.data_ptr(),
+                                                       counters.data_ptr(), _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    ms = e0.elapsed_time(e1)
+    return {
+        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
+        "ms": ms, "tflops": 2.0 * m * n * k / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
+    }
+
+
+def mx_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
+    """One FP8 / MXFP4 probe of a GPU: fill, then the GEMM with the check fused into its
+    epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
+    import torch
+
+    code = _mx_format(fmt)
+    if not mx_shape_ok(code, m, n, k):
+        raise ValueError("MX probe shape must be tile aligned")
+    dev = torch.device("cuda", device)
+    epb = 2 if code == ODH_MX_FP4 else 1
+    with torch.cuda.device(dev):
+        a = torch.empty((m, k // epb), dtype=torch.uint8, device=dev)
+        bt = torch.empty((n, k // epb), dtype=torch.uint8, device=dev)
+        sa = torch.empty((m, k // 32), dtype=torch.uint8, device=dev)
+        sbt = torch.empty((n, k // 32), dtype=torch.uint8, device=dev)
+        table = torch.empty(MX_TABLE, dtype=torch.float32, device=dev)
+        mx_fill(code, a, bt, sa, sbt, table)
+        return mx_verify(code, a, bt, sa, sbt, table)
 
 
 class GpuProbe:

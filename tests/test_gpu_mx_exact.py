@@ -1,0 +1,265 @@
+"""The block-scaled FP8 / MXFP4 probe kernels on a real MI355X against the host model
+(``mx_reference.py``): ``v_mfma_scale_f32_32x32x64_f8f6f4`` through ``odh_mx_gemm``,
+``odh_mx_fill``, ``odh_mx_probe_gemm_verify`` and ``odh-gpu-probe --mx``.
+
+Everything is bit-exact.  Operands are small dyadic numbers and scales powers of two, so every
+product is exact in fp32; each case checks on the CPU that ``sum_k |a| |b|`` stays below
+``2^24`` quanta, so every partial sum is representable and fp32 accumulation is exact in any
+order.  The tests corrupt data only; every pointer handed to a kernel comes from a torch
+allocation of exactly the size the shape implies.
+"""
+
+import faulthandler
+import functools
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mx_reference as ref
+
+torch = pytest.importorskip("torch")
+
+pytestmark = pytest.mark.gpu
+
+FORMATS = ["fp8", "fp4"]
+TEST_TIMEOUT_S = 60  # per test: a hung kernel ends the run here instead of holding the GPU
+
+
+@pytest.fixture(autouse=True)
+def _own_timeout():
+    faulthandler.dump_traceback_later(TEST_TIMEOUT_S, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a visible MI355X")
+    from odh_kubeflow_amd.ops import gpu
+
+    gpu.load_library()  # loud failure if the in-tree .so is missing
+    return torch.device("cuda", 0)
+
+
+def _gpu():
+    from odh_kubeflow_amd.ops import gpu
+
+    return gpu
+
+
+def _stage(fmt):
+    return 128 if fmt == "fp4" else 64  # elements per 64-byte stage of a row
+
+
+# ------------------------------------------------------------------ store kernel
+
+# every exactly representable value used: FP8 the integers -8 .. 8, FP4 all 15 values
+VALUES = {"fp8": np.arange(-8, 9, dtype=np.float64),
+          "fp4": np.concatenate([-ref.FP4_VALUES[:0:-1], ref.FP4_VALUES])}
+# the smallest product of two operands times two scales of 2^-2: the quantum of every sum
+QUANTUM = {"fp8": 2.0 ** -4, "fp4": 2.0 ** -6}
+
+
+@functools.lru_cache(maxsize=None)
+def _random_case(fmt, m, n, k):
+    """Seeded codes over ``VALUES``, scales 2^-2 .. 2^2, and the float64 product of the decoded,
+    scaled operands (decoded by ``mx_reference``, not by the encoder that made the codes)."""
+    rng = np.random.default_rng(1000003 * m + 1009 * n + k + ref.NAMES[fmt])
+    code = ref.NAMES[fmt]
+    a = ref.encode(code, rng.choice(VALUES[fmt], size=(m, k)))
+    bt = ref.encode(code, rng.choice(VALUES[fmt], size=(n, k)))
+    sa = rng.integers(125, 130, size=(m, k // 32), dtype=np.uint8)
+    sbt = rng.integers(125, 130, size=(n, k // 32), dtype=np.uint8)
+    xa, xb = ref.scaled(code, a, sa), ref.scaled(code, bt, sbt)
+    want = xa @ xb.T
+    # exact in fp32 in any summation order: every partial sum is a multiple of the quantum
+    # below 2^24 quanta (and float64 holds them with 29 bits to spare)
+    assert (np.abs(xa) @ np.abs(xb).T).max() < 2.0 ** 24 * QUANTUM[fmt]
+    return a, bt, sa, sbt, want
+
+
+def _exact_store(dev, fmt, m, n, k):
+    gpu = _gpu()
+    a, bt, sa, sbt, want = _random_case(fmt, m, n, k)
+    c = torch.full((m, n), float("nan"), device=dev)
+    t = [torch.from_numpy(x).to(dev) for x in (a, bt, sa, sbt)]
+    gpu.mx_gemm(fmt, *t, out=c)
+    got = c.cpu().double().numpy()
+    if not np.array_equal(got, want):
+        bad = np.argwhere(got != want)
+        pytest.fail(f"{fmt} {m}x{n}x{k}: {len(bad)} wrong elements, first at {bad[0].tolist()}: "
+                    f"{got[tuple(bad[0])]} != {want[tuple(bad[0])]}")
+
+
+# 1, 2, 3 and 5 stages (both buffers, odd and even counts) and a long K of 64 stages
+K_STAGES = [1, 2, 3, 5, 64]
+# one stage; workgroup counts = 0, 1 and 7 mod 8 (the XCD remap's three cases), then a single
+# tile row of 11
+GRIDS = [(512, 1024), (768, 768), (1280, 768), (256, 2816)]
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("stages", K_STAGES)
+def test_mx_gemm_exact_over_k(dev, fmt, stages):
+    _exact_store(dev, fmt, 256, 256, stages * _stage(fmt))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("m,n", GRIDS)
+def test_mx_gemm_exact_over_grids(dev, fmt, m, n):
+    _exact_store(dev, fmt, m, n, _stage(fmt))
+
+
+def test_mx_entry_points_check_before_launch(dev):
+    gpu = _gpu()
+    a, bt, sa, sbt, _ = _random_case("fp8", 256, 256, 64)
+    t = [torch.from_numpy(x).to(dev) for x in (a, bt, sa, sbt)]
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp6", *t)
+    with pytest.raises(TypeError):
+        gpu.mx_gemm("fp8", t[0].to(torch.int8), *t[1:])
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp8", t[0].cpu(), *t[1:])
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp8", t[0].t(), *t[1:])
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp4", *t)  # 64 bytes per row are 128 FP4 elements: the scales are [256, 4]
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp8", t[0][:128].contiguous(), *t[1:])
+    with pytest.raises(ValueError):
+        gpu.mx_gemm("fp8", *t[:3], t[3][:, :1].contiguous())
+
+
+# ------------------------------------------------------------------ fill
+
+
+def _filled(dev, fmt, m, n, k):
+    gpu = _gpu()
+    epb = 2 if fmt == "fp4" else 1
+    a = torch.full((m, k // epb), 0xEE, dtype=torch.uint8, device=dev)
+    bt = torch.full((n, k // epb), 0xEE, dtype=torch.uint8, device=dev)
+    sa = torch.zeros((m, k // 32), dtype=torch.uint8, device=dev)
+    sbt = torch.zeros((n, k // 32), dtype=torch.uint8, device=dev)
+    table = torch.full(gpu.MX_TABLE, float("nan"), device=dev)
+    gpu.mx_fill(fmt, a, bt, sa, sbt, table)
+    return a, bt, sa, sbt, table
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_mx_fill_matches_the_model(dev, fmt):
+    m, n, k = 256, 256, 384
+    a, bt, sa, sbt, table = _filled(dev, fmt, m, n, k)
+    va, vb = ref.probe_values(m, n, k)
+    code = ref.NAMES[fmt]
+    assert np.array_equal(a.cpu().numpy(), ref.encode(code, va))
+    assert np.array_equal(bt.cpu().numpy(), ref.encode(code, vb))
+    assert np.array_equal(ref.decode(code, a.cpu().numpy()), va)
+    assert np.array_equal(ref.decode(code, bt.cpu().numpy()), vb)
+    assert np.array_equal(sa.cpu().numpy(), ref.probe_scales(m, k))
+    assert np.array_equal(sbt.cpu().numpy(), ref.probe_scales(n, k))
+    t = ref.probe_table(k)
+    assert np.array_equal(table.cpu().double().numpy(), t)
+    # the table is the product of the operands as filled: the closed form holds
+    want = ref.product(code, a.cpu().numpy(), bt.cpu().numpy(), sa.cpu().numpy(), sbt.cpu().numpy())
+    assert np.array_equal(want, t[np.arange(m)[:, None] % ref.ROWS, np.arange(n)[None, :] % ref.COLS])
+
+
+# ------------------------------------------------------------------ fused verify
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("m,n,k", [(256, 256, 256), (512, 768, 384), (1280, 768, 1024)])
+def test_mx_verify_clean(dev, fmt, m, n, k):
+    gpu = _gpu()
+    assert ref.zero_classes(k) == 0
+    r = gpu.mx_verify(fmt, *_filled(dev, fmt, m, n, k))
+    assert r["errors"] == 0 and sum(r["err_xcd"]) == 0, r
+    assert sum(r["xcd_blocks"]) == (m // 256) * (n // 256), r
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_mx_verify_finds_a_corrupted_operand(dev, fmt):
+    """``A[0][0]`` becomes +3 as ``--inject-fault mx`` makes it (``A[0][1]`` is 0, so the FP4 byte
+    is 0x05): row 0 is wrong exactly where ``Bt[j][0] = ((11 j) mod 7) - 3`` is non-zero."""
+    gpu = _gpu()
+    m, n, k = 256, 256, 256
+    a, bt, sa, sbt, table = _filled(dev, fmt, m, n, k)
+    a[0, 0] = 0x05 if fmt == "fp4" else 0x44
+    want = sum(1 for j in range(n) if (11 * j) % 7 != 3)
+    assert want == 220
+    r = gpu.mx_verify(fmt, a, bt, sa, sbt, table)
+    assert r["errors"] == want and sum(r["err_xcd"]) == want, r
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_mx_verify_reads_each_blocks_scale(dev, fmt):
+    """Scale byte ``sA[0][0]`` goes from 126 to 130: only the first 32 k of row 0 change weight,
+    and the mismatches are the columns where the model's row 0 then differs from the table."""
+    gpu = _gpu()
+    m, n, k = 256, 256, 256
+    a, bt, sa, sbt, table = _filled(dev, fmt, m, n, k)
+    assert int(sa[0, 0]) == 126
+    sa[0, 0] = 130
+    code = ref.NAMES[fmt]
+    row = ref.product(code, a[:1].cpu().numpy(), bt.cpu().numpy(), sa[:1].cpu().numpy(), sbt.cpu().numpy())[0]
+    want = int((row != ref.probe_table(k)[0, np.arange(n) % ref.COLS]).sum())
+    assert 0 < want < n
+    r = gpu.mx_verify(fmt, a, bt, sa, sbt, table)
+    assert r["errors"] == want and sum(r["err_xcd"]) == want, r
+
+
+def test_mx_probe_reports_the_check(dev):
+    r = _gpu().mx_probe(0, "fp8", 512, 512, 256)
+    assert set(r) >= {"errors", "err_xcd", "xcd_blocks", "ms", "tflops"}
+    assert r["errors"] == 0 and sum(r["xcd_blocks"]) == 4 and r["ms"] > 0
+
+
+# ------------------------------------------------------------------ the program
+
+
+def _run_probe(*args, timeout=120):
+    from odh_kubeflow_amd.ops import probe_main
+
+    exe = probe_main.executable()
+    if not os.path.exists(exe):
+        pytest.fail("odh-gpu-probe not built: python -m odh_kubeflow_amd.ops.build")
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("HIP_VISIBLE", "ROCR_VISIBLE", "CUDA_VISIBLE"))}
+    env["HIP_VISIBLE_DEVICES"] = "0"
+    r = subprocess.run(["timeout", "-k", "10", str(timeout), exe, "--json", "-", *args], capture_output=True,
+                       text=True, env=env, timeout=timeout + 20)
+    return r.returncode, probe_main.parse_result(r.stdout), r
+
+
+def test_mx_program_passes_on_the_mi355x():
+    rc, res, r = _run_probe("--mx", "fp8,fp4")
+    assert rc == 0, (r.stdout, r.stderr)
+    assert res["ok"] and set(res["mx"]) == {"fp8", "fp4"}
+    for fmt in FORMATS:
+        f = res["mx"][fmt]
+        assert f["ok"] is True and f["errors"] == 0, res["mx"]
+        assert f["tflops"] > 50 and f["ms"] > 0 and f["host_ms"] > 0, res["mx"]  # the matrix cores, not a stub
+    d = res["results"][0]
+    assert d["gemm_errors"] == 0 and d["hbm_errors"] == 0
+    assert len(json.dumps(res["mx"], separators=(",", ":"))) < 256
+    assert len(r.stdout.strip().splitlines()[-1]) < 4096
+    print("mx:", json.dumps(res["mx"]), "timings_ms:", json.dumps(res["timings_ms"]))
+
+
+def test_mx_program_fails_on_injected_fault():
+    from odh_kubeflow_amd.ops import probe_main
+
+    rc, res, r = _run_probe("--mx", "fp8,fp4", "--inject-fault", "mx")
+    assert rc == probe_main.CHECK_FAILED, (r.stdout, r.stderr)
+    want = sum(1 for j in range(4096) if (11 * j) % 7 != 3)
+    assert want == 3511
+    assert res["ok"] is False
+    for fmt in FORMATS:
+        assert res["mx"][fmt]["ok"] is False and res["mx"][fmt]["errors"] == want, res["mx"]
+    assert "GPU 0" in res["error"] and "fp8" in res["error"] and "XCD" in res["error"], res["error"]
+    d = res["results"][0]
+    assert d["gemm_errors"] == 0 and d["hbm_errors"] == 0, d
+    assert len(r.stdout.strip().splitlines()[-1]) < 4096
