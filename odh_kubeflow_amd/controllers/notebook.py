@@ -24,7 +24,7 @@ pods that request GPUs also get the AMD node-labeller selector and the
 gets a memory-backed one of that size per GPU: PyTorch DataLoader workers and RCCL's
 intra-node transport live there, and the container default (64 MiB) breaks both.  The
 ``amd.com/shm-size`` annotation overrides the size (``0`` turns it off).  With
-``amd.com/gpu-probe: "true"`` on the Notebook (a comma list of ``true``, ``rccl``, ``mx``; or
+``amd.com/gpu-probe: "true"`` on the Notebook (a comma list of ``true``, ``rccl``, ``mx``, ``dtypes``; or
 ``GPU_STARTUP_PROBE=true`` for every GPU notebook) the pod gets the ``amd-gpu-probe`` init
 container: the MI355X start-up probe
 (``odh-gpu-probe``, ``GPU_PROBE_IMAGE``) on the GPUs the device plugin gives it, before the
@@ -177,16 +177,17 @@ DEFAULT_GPU_PROBE_IMAGE = "quay.io/opendatahub/odh-kubeflow-amd-gpu-probe:main" 
 GPU_PROBE_TIMEOUT_MS = "30000"
 GPU_PROBE_RCCL_MIB = "64"  # all-reduce size of the RCCL step (annotation token "rccl")
 GPU_PROBE_MX_FORMATS = "fp8,fp4"  # block-scaled formats of the MX step (annotation token "mx")
+GPU_PROBE_DTYPES_FORMATS = "f16,i8"  # dense formats of the dtypes step (annotation token "dtypes")
 
 
-GPU_PROBE_TOKENS = ("true", "rccl", "mx", "false")
+GPU_PROBE_TOKENS = ("true", "rccl", "mx", "dtypes", "false")
 
 
 def gpu_probe_tokens(nb: dict) -> frozenset:
     """The ``amd.com/gpu-probe`` annotation as a set of tokens.  It is a comma list of ``true``,
-    ``rccl``, ``mx`` and ``false``: ``rccl`` and ``mx`` each turn the probe on and add their step,
-    so ``"rccl,mx"`` runs both.  A value with an unknown token, or with ``false`` next to another
-    token, is ignored as a whole (the empty set), like an unknown value."""
+    ``rccl``, ``mx``, ``dtypes`` and ``false``: ``rccl``, ``mx`` and ``dtypes`` each turn the probe on
+    and add their step, so ``"rccl,mx"`` runs both.  A value with an unknown token, or with
+    ``false`` next to another token, is ignored as a whole (the empty set), like an unknown value."""
     v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
     tokens = frozenset(t.strip() for t in v.split(",")) if v else frozenset()
     if not tokens <= frozenset(GPU_PROBE_TOKENS) or ("false" in tokens and len(tokens) > 1):
@@ -196,8 +197,8 @@ def gpu_probe_tokens(nb: dict) -> frozenset:
 
 def gpu_probe_enabled(nb: dict, pod_spec: dict, env: Mapping[str, str] = os.environ) -> bool:
     """The MI355X start-up probe runs for notebooks that request ``amd.com/gpu`` when the
-    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, or a comma list of
-    them), or when the operator turned it on for every GPU notebook (``GPU_STARTUP_PROBE=true``)
+    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, ``"dtypes"``, or a comma
+    list of them), or when the operator turned it on for every GPU notebook (``GPU_STARTUP_PROBE=true``)
     and the Notebook does not say ``"false"``.  Off by default (never on the
     reconcile path, opt-in)."""
     if gpu_request(pod_spec) <= 0:
@@ -221,16 +222,22 @@ def gpu_probe_mx(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
     return "mx" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_MX", "false") == "true"
 
 
+def gpu_probe_dtypes(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
+    """Whether the probe also checks the FP16 and INT8 matrix cores (``--dtypes f16,i8``):
+    ``dtypes`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_DTYPES=true`` for every probed notebook."""
+    return "dtypes" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_DTYPES", "false") == "true"
+
+
 def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False,
-                             mx: bool = False) -> dict:
+                             mx: bool = False, dtypes: bool = False) -> dict:
     """Init container that proves the pod's GPUs healthy before the notebook starts.
 
     ``odh-gpu-probe`` (``ops/csrc/probe_cli.cpp``, torch-free) runs the bf16 MFMA GEMM checked
     in registers and the HBM3E pattern sweep on every GPU the device plugin gives the pod, and
     with 2+ GPUs reads the xGMI ring between them (``rccl``: plus an RCCL all-reduce over all
     of them, ``--rccl-mib``; ``mx``: plus the FP8 and MXFP4 block-scaled GEMMs checked the same
-    way, ``--mx fp8,fp4``); non-zero exit keeps the pod in Init, and its
-    JSON verdict is the container's termination message.  It asks for the same
+    way, ``--mx fp8,fp4``; ``dtypes``: plus the FP16 and INT8 GEMMs, ``--dtypes f16,i8``);
+    non-zero exit keeps the pod in Init, and its JSON verdict is the container's termination message.  It asks for the same
     ``amd.com/gpu`` count as the notebook: the kubelet device manager hands an init
     container's devices on to the app containers, so the GPUs probed are the GPUs the
     notebook gets, and the pod's effective request (max of init and app) does not grow."""
@@ -240,6 +247,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
         args += ["--rccl-mib", GPU_PROBE_RCCL_MIB]
     if mx:
         args += ["--mx", GPU_PROBE_MX_FORMATS]
+    if dtypes:  # after the --mx arguments: every argument list without it stays as it was
+        args += ["--dtypes", GPU_PROBE_DTYPES_FORMATS]
     return {
         "name": GPU_PROBE_CONTAINER,
         "image": env.get("GPU_PROBE_IMAGE") or DEFAULT_GPU_PROBE_IMAGE,
@@ -260,7 +269,8 @@ def _gpu_probe(nb: dict, pod_spec: dict, env: Mapping[str, str]) -> None:
         return  # the user brought their own
     n = gpu_request(pod_spec)
     # before any init container that uses the GPU
-    inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env), mx=gpu_probe_mx(nb, env)))
+    inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env), mx=gpu_probe_mx(nb, env),
+                                             dtypes=gpu_probe_dtypes(nb, env)))
 
 
 def generate_statefulset(nb: dict, is_generate_name: bool, env: Mapping[str, str] = os.environ) -> dict:

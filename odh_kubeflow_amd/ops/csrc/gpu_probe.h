@@ -30,6 +30,11 @@ enum {
   ODH_MX_FP8 = 0,  // OCP e4m3fn, one byte per element
   ODH_MX_FP4 = 4,  // e2m1, two elements per byte (even k in the low nibble)
   ODH_MX_CLASSES = 315,  // floats in the table of expected values: (i mod 15, j mod 21)
+  // operand formats of the dense FP16 / INT8 kernels (gpu_probe_dense.h)
+  ODH_DT_F16 = 1,  // IEEE half, fp32 accumulation
+  ODH_DT_I8 = 2,   // int8, int32 accumulation
+  ODH_DT_I8_MUL_A = 25,  // the i8 probe operands: these odd multiples of the bf16 probe's A ...
+  ODH_DT_I8_MUL_B = 41,  // ... and Bt, so the expected product is 1025 × the bf16 probe's
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -83,6 +88,13 @@ int odh_mx_gemm(int fmt, const void* A, const void* Bt, const void* sA, const vo
 int odh_mx_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt,
                              const float* table, int M, int N, int K, int* tile_xcd, int* counters,
                              hipStream_t stream);
+// Dense FP16 / INT8 (fmt: ODH_DT_*): A [M][K] and Bt [N][K] halves or int8 (16-byte aligned), C [M][N] fp32
+// (f16) or int32 (i8); M and N multiples of 256, K of 32 (f16) or 64 (i8); counters: ODH_NCOUNT × i32 of
+// this format's own on the device (slots ODH_SLOT_XCD_BLOCKS, ODH_SLOT_ERR_XCD, ODH_SLOT_GEMM_ERR)
+int odh_dense_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t stream);
+int odh_dense_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream);
+int odh_dense_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
+                                int* counters, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

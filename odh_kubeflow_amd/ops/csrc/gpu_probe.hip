@@ -32,6 +32,9 @@
 //  * odh_mx_fill / odh_mx_gemm / odh_mx_probe_gemm_verify — the same exact check on the
 //    block-scaled FP8 / MXFP4 path (v_mfma_scale_f32_32x32x64_f8f6f4; gpu_probe_mx.h), and
 //    odh_mx_zero_classes, the host-side guard against a K at which that check is blind.
+//  * odh_dense_fill / odh_dense_gemm / odh_dense_probe_gemm_verify — the same exact check on the
+//    FP16 and INT8 paths (v_mfma_f32_32x32x16_f16, v_mfma_i32_32x32x32_i8; gpu_probe_dense.h):
+//    the deep-pipelined 256² tile again, with halves or int8 in its 64-byte stage rows.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -577,6 +580,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
 }
 
 #include "gpu_probe_mx.h"  // the FP8 / MXFP4 block-scaled kernels, on the tile helpers above
+#include "gpu_probe_dense.h"  // the FP16 / INT8 kernels, on the same helpers and the ring above
 
 __device__ __forceinline__ uint16_t small_int_bf16(int v) {
   // exact for |v| < 256: take the high half of the f32 bit pattern
@@ -1188,6 +1192,47 @@ int odh_mx_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void*
     mx_gemm256_kernel<ODH_MX_FP8, true><<<nwg, G_THREADS, 0, stream>>>(
         (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, nullptr, table, N, K, tile_xcd,
         counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ FP16 / INT8 (gpu_probe_dense.h)
+
+// the probe operands as halves, or as int8 times ODH_DT_I8_MUL_A / _B
+int odh_dense_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t stream) {
+  if (!dense_ok(fmt, M, N, K) || !dense_aligned(A, Bt)) return (int)hipErrorInvalidValue;
+  const size_t n = ((size_t)M + N) * (size_t)K;
+  dense_fill_kernel<<<grid_for(n, 256), 256, 0, stream>>>(fmt, A, Bt, M, N, K);
+  return (int)hipGetLastError();
+}
+
+// C[M][N] = A · Btᵀ for any operands: fp32 out of halves, int32 out of int8
+int odh_dense_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream) {
+  if (!dense_ok(fmt, M, N, K) || !dense_aligned(A, Bt) || !C || ((uintptr_t)C & 3)) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
+  if (fmt == ODH_DT_I8)
+    dense_gemm256_kernel<ODH_DT_I8, false><<<nwg, G_THREADS, 0, stream>>>((const uint4*)A, (const uint4*)Bt, C, N, K,
+                                                                          nullptr, nullptr, nullptr, nullptr);
+  else
+    dense_gemm256_kernel<ODH_DT_F16, false><<<nwg, G_THREADS, 0, stream>>>((const uint4*)A, (const uint4*)Bt, C, N, K,
+                                                                           nullptr, nullptr, nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+// the same tiles on odh_dense_fill's operands with the check against the closed form fused into
+// the epilogue; counters is a counter block of this format's own
+int odh_dense_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
+                                int* counters, hipStream_t stream) {
+  if (!dense_ok(fmt, M, N, K) || !dense_aligned(A, Bt) || !counters) return (int)hipErrorInvalidValue;
+  const int nwg = gemm256_tiles(M, N);
+  unsigned* c = (unsigned*)counters;
+  if (fmt == ODH_DT_I8)
+    dense_gemm256_kernel<ODH_DT_I8, true><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, nullptr, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+        c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  else
+    dense_gemm256_kernel<ODH_DT_F16, true><<<nwg, G_THREADS, 0, stream>>>(
+        (const uint4*)A, (const uint4*)Bt, nullptr, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+        c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

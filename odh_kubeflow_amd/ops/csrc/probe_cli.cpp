@@ -22,7 +22,12 @@
 //      its stream, per format: the probe operands re-encoded as FP8 / MXFP4 codes with E8M0
 //      block scales into the bf16 operands' buffers (odh_mx_fill), then the block-scaled GEMM
 //      (v_mfma_scale_f32_32x32x64_f8f6f4) checked in registers against a 15 × 21 table
-//      (odh_mx_probe_gemm_verify): the data path a quantised model runs on.
+//      (odh_mx_probe_gemm_verify): the data path a quantised model runs on;
+//   6. with --dtypes f16,i8 (the `amd.com/gpu-probe: "dtypes"` notebooks), after the HBM sweep, on
+//      its stream and before step 5, per format: the probe operands re-encoded as halves or as
+//      int8 (odh_dense_fill) into the bf16 operands' buffers, then the FP16
+//      (v_mfma_f32_32x32x16_f16) or INT8 (v_mfma_i32_32x32x32_i8) GEMM checked in registers against
+//      the closed form (odh_dense_probe_gemm_verify): autocast's default dtype and the W8A8 path.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -69,8 +74,9 @@ struct Options {
   size_t rccl_bytes = 0;  // 0: no RCCL step
   long timeout_ms = 30000;
   std::string json_path;  // "" = default; "-" = stdout only
-  std::string fault;      // test hook: gemm | hbm | xgmi | rccl | mx
+  std::string fault;      // test hook: gemm | hbm | xgmi | rccl | mx | dtypes
   std::vector<int> mx;    // --mx: ODH_MX_* formats to check, in the order given
+  std::vector<int> dtypes;  // --dtypes: ODH_DT_* formats to check, in the order given
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
   // 1 = one stream, 2 = the HBM sweep overlapping the GEMM on a second stream.  Each stream is
@@ -102,15 +108,22 @@ struct Dev {
   int mx_host[2][ODH_NCOUNT] = {};
   hipEvent_t e_mx0[2] = {}, e_mx1[2] = {};
   float mx_ms[2] = {};
+  // --dtypes: one counter block (behind the MX ones) and event pair per format
+  int* dt_counters = nullptr;
+  int dt_host[2][ODH_NCOUNT] = {};
+  hipEvent_t e_dt0[2] = {}, e_dt1[2] = {};
+  float dt_ms[2] = {};
   std::string error;
 };
 
 const char* mx_name(int fmt) { return fmt == ODH_MX_FP4 ? "fp4" : "fp8"; }
+const char* dt_name(int fmt) { return fmt == ODH_DT_I8 ? "i8" : "f16"; }
 
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
-               "[--mx fp8,fp4] [--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx] [--quiet]\n",
+               "[--mx fp8,fp4] [--dtypes f16,i8] [--timeout-ms N] [--streams 0|1|2] "
+               "[--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes] [--quiet]\n",
                argv0);
   return 64;
 }
@@ -144,7 +157,7 @@ bool parse(int argc, char** argv, Options& o) {
       if (o.streams < 0 || o.streams > 2) return false;
     } else if (a == "--inject-fault") {
       o.fault = v;
-      if (v != "gemm" && v != "hbm" && v != "xgmi" && v != "rccl" && v != "mx") return false;
+      if (v != "gemm" && v != "hbm" && v != "xgmi" && v != "rccl" && v != "mx" && v != "dtypes") return false;
     } else if (a == "--mx") {
       // a comma list of formats, each at most once
       for (size_t at = 0; at <= v.size();) {
@@ -153,6 +166,16 @@ bool parse(int argc, char** argv, Options& o) {
         const int fmt = name == "fp8" ? ODH_MX_FP8 : name == "fp4" ? ODH_MX_FP4 : -1;
         if (fmt < 0 || std::find(o.mx.begin(), o.mx.end(), fmt) != o.mx.end()) return false;
         o.mx.push_back(fmt);
+        at = comma + 1;
+      }
+    } else if (a == "--dtypes") {
+      // the same kind of list
+      for (size_t at = 0; at <= v.size();) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string name = v.substr(at, comma - at);
+        const int fmt = name == "f16" ? ODH_DT_F16 : name == "i8" ? ODH_DT_I8 : -1;
+        if (fmt < 0 || std::find(o.dtypes.begin(), o.dtypes.end(), fmt) != o.dtypes.end()) return false;
+        o.dtypes.push_back(fmt);
         at = comma + 1;
       }
     } else if (a == "--quiet") {
@@ -169,6 +192,9 @@ bool parse(int argc, char** argv, Options& o) {
   // operands may expect 0 at it (odh_mx_zero_classes: host arithmetic, before any HIP call)
   if (!o.mx.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
   if (o.fault == "mx" && o.mx.empty()) return false;
+  // --dtypes: the operands are the bf16 probe's (times constants for i8), so the K rules below
+  // cover it: K % 64 == 0 is a whole number of f16 and of i8 stages, K % 35 != 0 a non-zero product
+  if (o.fault == "dtypes" && o.dtypes.empty()) return false;
   return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 && o.K % 35 != 0 &&
          o.hbm_bytes >= (1u << 20) && o.timeout_ms > 0 && 2 * o.rccl_bytes <= o.hbm_bytes &&
          (o.fault != "rccl" || o.rccl_bytes > 0);
@@ -232,7 +258,8 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
   // --mx adds a counter block per format behind the first, the scales of both operands and the table
-  const size_t nmx = o.mx.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nmx));
+  // --dtypes adds one more per format behind those, and nothing else: its operands are no larger
+  const size_t nmx = o.mx.size(), ndt = o.dtypes.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nmx + ndt));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
   HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab));
@@ -249,6 +276,7 @@ bool setup_alloc(Dev& d, const Options& o) {
     d.mx_sbt = p + na + nb + nh + nt + nc + nsa;
     d.mx_table = (float*)(p + na + nb + nh + nt + nc + nsa + nsb);
   }
+  if (ndt) d.dt_counters = d.counters + ODH_NCOUNT * (1 + nmx);
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -261,11 +289,15 @@ bool setup_alloc(Dev& d, const Options& o) {
     HIP_TRY(hipEventCreate(&d.e_mx0[f]));
     HIP_TRY(hipEventCreate(&d.e_mx1[f]));
   }
+  for (size_t f = 0; f < ndt; ++f) {
+    HIP_TRY(hipEventCreate(&d.e_dt0[f]));
+    HIP_TRY(hipEventCreate(&d.e_dt1[f]));
+  }
   d.events_ms = ms_since(t0);
   // the first operation on the stream: on the null stream it creates the hardware queue, here
   // while the other thread is still loading the code object
   t0 = Clock::now();
-  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nmx), d.sg));
+  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nmx + ndt), d.sg));
   d.first_op_ms = ms_since(t0);
   return true;
 }
@@ -347,6 +379,38 @@ bool mx_finish(Dev& d, size_t f) {
   return true;
 }
 
+// format f of --dtypes on the sweep's stream, after the sweep and before --mx: the operands
+// re-encoded into the bf16 operands' buffers (halves are as large, int8 half as large), then the
+// fused check
+bool dt_launch(Dev& d, const Options& o, size_t f) {
+  const int fmt = o.dtypes[f];
+  int* counters = d.dt_counters + f * ODH_NCOUNT;
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_dense_fill(fmt, d.a, d.bt, o.M, o.N, o.K, d.sh));
+  if (o.fault == "dtypes") {
+    // A[0][0] becomes +1 (the half 0x3C00, or the int8 25 = 1 × ODH_DT_I8_MUL_A): row 0 of C is
+    // wrong wherever Bt[j][0] != 0
+    if (fmt == ODH_DT_I8) {
+      HIP_TRY(hipMemsetAsync(d.a, ODH_DT_I8_MUL_A, 1, d.sh));
+    } else {
+      HIP_TRY(hipMemsetAsync(d.a, 0x00, 1, d.sh));
+      HIP_TRY(hipMemsetAsync((char*)d.a + 1, 0x3C, 1, d.sh));
+    }
+  }
+  HIP_TRY(hipEventRecord(d.e_dt0[f], d.sh));
+  HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, counters, d.sh));
+  HIP_TRY(hipEventRecord(d.e_dt1[f], d.sh));
+  HIP_TRY(hipMemcpyAsync(d.dt_host[f], counters, sizeof d.dt_host[f], hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+bool dt_finish(Dev& d, size_t f) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(hipStreamSynchronize(d.sh));
+  HIP_TRY(hipEventElapsedTime(&d.dt_ms[f], d.e_dt0[f], d.e_dt1[f]));
+  return true;
+}
+
 // reader d checks source s's freshly written pattern over xGMI
 bool link_check(Dev& d, const Dev& s, const Options& o) {
   HIP_TRY(odh_peer_enable(d.index, s.index));
@@ -377,6 +441,8 @@ void release(Dev& d) {
   for (int f = 0; f < 2; ++f) {
     if (d.e_mx0[f]) (void)hipEventDestroy(d.e_mx0[f]);
     if (d.e_mx1[f]) (void)hipEventDestroy(d.e_mx1[f]);
+    if (d.e_dt0[f]) (void)hipEventDestroy(d.e_dt0[f]);
+    if (d.e_dt1[f]) (void)hipEventDestroy(d.e_dt1[f]);
   }
   if (d.sh && d.sh != d.sg) (void)hipStreamDestroy(d.sh);
   if (d.sg) (void)hipStreamDestroy(d.sg);
@@ -602,7 +668,19 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --mx: one format at a time over every device, so each format has a host time of its own
+  // --dtypes, then --mx: one format at a time over every device, so each format has a host time
+  // of its own
+  double dt_host_ms[2] = {};
+  const auto t_dt0 = Clock::now();
+  for (size_t f = 0; f < o.dtypes.size(); ++f) {
+    const auto t0 = Clock::now();
+    for (Dev& d : devs)
+      if (!dt_launch(d, o, f)) return fail_all(d);
+    for (Dev& d : devs)
+      if (!dt_finish(d, f)) return fail_all(d);
+    dt_host_ms[f] = ms_since(t0);
+  }
+  const double dt_total_ms = ms_since(t_dt0);
   double mx_host_ms[2] = {};
   const auto t_mx0 = Clock::now();
   for (size_t f = 0; f < o.mx.size(); ++f) {
@@ -709,49 +787,60 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                   ndev > 1 ? algbw * 2.0 * (ndev - 1) / ndev : algbw);
     rccl = b;
   }
-  // per format, whatever the device count: total mismatches, the slowest device's kernel time
-  std::string mx;
-  for (size_t f = 0; f < o.mx.size(); ++f) {
-    uint64_t errs = 0;
-    float slowest = 0;
-    bool fok = true;
-    for (Dev& d : devs) {
-      const int* h = d.mx_host[f];
-      long blocks = 0;
-      std::string where;
-      for (int x = 0; x < ODH_N_XCD; ++x) {
-        blocks += h[ODH_SLOT_XCD_BLOCKS + x];
-        if (h[ODH_SLOT_ERR_XCD + x]) where += (where.empty() ? "" : ",") + std::to_string(x);
+  // the object of an optional GEMM step (--mx, --dtypes), "" without it: per format, whatever the
+  // device count, total mismatches and the slowest device's kernel time
+  auto step_json = [&](const char* key, const std::vector<int>& fmts, const char* (*name)(int), const char* what,
+                       int (Dev::*host)[2][ODH_NCOUNT], float (Dev::*ms)[2], const double* host_ms) {
+    std::string out;
+    for (size_t f = 0; f < fmts.size(); ++f) {
+      uint64_t errs = 0;
+      float slowest = 0;
+      bool fok = true;
+      for (Dev& d : devs) {
+        const int* h = (d.*host)[f];
+        long blocks = 0;
+        std::string where;
+        for (int x = 0; x < ODH_N_XCD; ++x) {
+          blocks += h[ODH_SLOT_XCD_BLOCKS + x];
+          if (h[ODH_SLOT_ERR_XCD + x]) where += (where.empty() ? "" : ",") + std::to_string(x);
+        }
+        const uint32_t e = (uint32_t)h[ODH_SLOT_GEMM_ERR];
+        errs += e;
+        slowest = (d.*ms)[f] > slowest ? (d.*ms)[f] : slowest;
+        if (e == 0 && blocks == tiles) continue;
+        fok = false;
+        if (first_err.empty()) {
+          char b[200];
+          std::snprintf(b, sizeof b, "GPU %d: %s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index, name(fmts[f]), e,
+                        what, where.empty() ? "-" : where.c_str(), blocks, tiles);
+          first_err = b;
+        }
       }
-      const uint32_t e = (uint32_t)h[ODH_SLOT_GEMM_ERR];
-      errs += e;
-      slowest = d.mx_ms[f] > slowest ? d.mx_ms[f] : slowest;
-      if (e == 0 && blocks == tiles) continue;
-      fok = false;
-      if (first_err.empty()) {
-        char b[200];
-        std::snprintf(b, sizeof b, "GPU %d: %s: %u MX GEMM mismatches on XCD %s, %ld/%d tiles", d.index, mx_name(o.mx[f]),
-                      e, where.empty() ? "-" : where.c_str(), blocks, tiles);
-        first_err = b;
-      }
+      ok = ok && fok;
+      char b[128];
+      std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"tflops\":%.1f,\"host_ms\":%.3f}",
+                    f ? "," : (std::string(",\"") + key + "\":{").c_str(), name(fmts[f]), fok ? "true" : "false",
+                    (unsigned long long)errs, slowest, slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, host_ms[f]);
+      out += b;
     }
-    ok = ok && fok;
-    char b[128];
-    std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"tflops\":%.1f,\"host_ms\":%.3f}",
-                  f ? "," : ",\"mx\":{", mx_name(o.mx[f]), fok ? "true" : "false", (unsigned long long)errs, slowest,
-                  slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, mx_host_ms[f]);
-    mx += b;
-  }
-  if (!mx.empty()) mx += "}";
+    return out.empty() ? out : out + "}";
+  };
+  const std::string mx = step_json("mx", o.mx, mx_name, "MX GEMM", &Dev::mx_host, &Dev::mx_ms, mx_host_ms);
+  // tflops counts integer operations for i8
+  const std::string dt = step_json("dtypes", o.dtypes, dt_name, "GEMM", &Dev::dt_host, &Dev::dt_ms, dt_host_ms);
   for (Dev& d : devs) release(d);
-  char mx_timing[48] = "";
-  if (!o.mx.empty()) std::snprintf(mx_timing, sizeof mx_timing, "\"mx\":%.3f,", mx_total_ms);
+  char step_timing[96] = "";
+  if (!o.mx.empty()) std::snprintf(step_timing, sizeof step_timing, "\"mx\":%.3f,", mx_total_ms);
+  if (!o.dtypes.empty()) {
+    const size_t at = std::strlen(step_timing);
+    std::snprintf(step_timing + at, sizeof step_timing - at, "\"dtypes\":%.3f,", dt_total_ms);
+  }
   char tail[512];
   std::snprintf(tail, sizeof tail,
                 ",\"timings_ms\":{\"exec\":%.3f,\"hip_init\":%.3f,\"alloc_fill\":%.3f,\"alloc\":%.3f,"
                 "\"code_load\":%.3f,\"fill\":%.3f,\"probe\":%.3f,\"xgmi\":%.3f,\"rccl\":%.3f,%s\"total\":%.3f}}",
                 t_exec, t_init, t_alloc - t_init, t_alloc_only - t_init, t_preload - t_init, t_alloc - t_malloc, probe_ms,
-                link_ms, rr.load_ms + rr.init_ms + rr.wall_ms, mx_timing, ms_since(t_start));
+                link_ms, rr.load_ms + rr.init_ms + rr.wall_ms, step_timing, ms_since(t_start));
   char setup[192];
   std::snprintf(setup, sizeof setup,
                 ",\"setup_ms\":{\"malloc\":%.3f,\"streams\":%.3f,\"events\":%.3f,\"first_op\":%.3f,\"n_streams\":%d}",
@@ -760,6 +849,6 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                      ",\"shape\":[" + std::to_string(o.M) + "," + std::to_string(o.N) + "," + std::to_string(o.K) +
                      "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
                      (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
-                     ",\"links\":" + links + rccl + mx + setup + tail;
+                     ",\"links\":" + links + rccl + mx + dt + setup + tail;
   return done(ok ? 0 : 1, json);
 }

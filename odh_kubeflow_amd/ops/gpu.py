@@ -17,6 +17,9 @@
 * :func:`mx_fill`, :func:`mx_gemm`, :func:`mx_probe` — the block-scaled FP8 / MXFP4 path of the
   matrix cores (``v_mfma_scale_f32_32x32x64_f8f6f4``) on uint8 code tensors: the same exact
   in-register check, against a 15 × 21 table (``odh-gpu-probe --mx``).
+* :func:`dense_fill`, :func:`dense_gemm`, :func:`dense_probe` — the FP16 and INT8 paths
+  (``v_mfma_f32_32x32x16_f16``, ``v_mfma_i32_32x32x32_i8``) on float16 / int8 tensors: the same
+  check against the bf16 probe's 5 × 7 closed form (``odh-gpu-probe --dtypes``).
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
@@ -65,6 +68,12 @@ ODH_MX_FP4 = 4  # e2m1, two elements per byte (even k in the low nibble)
 ODH_MX_CLASSES = 315  # floats in the table of expected values
 MX_FORMATS = {"fp8": ODH_MX_FP8, "fp4": ODH_MX_FP4}
 MX_TABLE = (15, 21)  # expected values of the MX probe operands, by (i mod 15, j mod 21)
+# operand formats of the dense FP16 / INT8 kernels (csrc/gpu_probe_dense.h)
+ODH_DT_F16 = 1  # IEEE half, fp32 accumulation
+ODH_DT_I8 = 2  # int8, int32 accumulation
+ODH_DT_I8_MUL_A = 25  # the i8 probe operands are these odd multiples of the bf16 probe's A ...
+ODH_DT_I8_MUL_B = 41  # ... and Bt: the expected product is 1025 × the bf16 probe's
+DENSE_FORMATS = {"f16": ODH_DT_F16, "i8": ODH_DT_I8}
 
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -97,6 +106,10 @@ SIGNATURES = {
     "odh_mx_fill": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_mx_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_mx_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # dense FP16 / INT8 (csrc/gpu_probe_dense.h)
+    "odh_dense_fill": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_dense_gemm": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_dense_probe_gemm_verify": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -338,6 +351,109 @@ def mx_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1],
         table = torch.empty(MX_TABLE, dtype=torch.float32, device=dev)
         mx_fill(code, a, bt, sa, sbt, table)
         return mx_verify(code, a, bt, sa, sbt, table)
+
+
+def _dense_format(fmt) -> int:
+    code = DENSE_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in DENSE_FORMATS.values():
+        raise ValueError(f"dense format must be one of {sorted(DENSE_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def dense_shape_ok(fmt, m: int, n: int, k: int) -> bool:
+    """256² output tiles, and K in stages of 64 bytes per row: 32 halves or 64 int8."""
+    bk = 64 if _dense_format(fmt) == ODH_DT_I8 else 32
+    return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
+
+
+def _dense_operands(fmt, a, bt):
+    """Checks of the dense entry points, before launch: float16 (f16) or int8 (i8), one GPU,
+    contiguous, A ``[M, K]`` and Bt ``[N, K]``.  Returns the format code and M, N, K."""
+    import torch
+
+    code = _dense_format(fmt)
+    want = torch.int8 if code == ODH_DT_I8 else torch.float16
+    if a.dtype != want or bt.dtype != want:
+        raise TypeError(f"{'i8' if code == ODH_DT_I8 else 'f16'} operands are {want}")
+    if a.dim() != 2 or bt.dim() != 2:
+        raise ValueError("dense operands are 2-D")
+    if not (a.is_cuda and bt.is_cuda) or a.device != bt.device:
+        raise ValueError("operands must live on the same GPU")
+    if not (a.is_contiguous() and bt.is_contiguous()):
+        raise ValueError("operands must be contiguous")
+    m, k = a.shape
+    n = bt.shape[0]
+    if bt.shape[1] != k or not dense_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {64 if code == ODH_DT_I8 else 32}; "
+                         f"got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    return code, m, n, k
+
+
+def dense_fill(fmt, a, bt) -> None:
+    """The probe operands for ``fmt`` written into the given tensors: exact halves (``"f16"``), or
+    int8 times ``ODH_DT_I8_MUL_A`` / ``ODH_DT_I8_MUL_B`` (``"i8"``)."""
+    code, m, n, k = _dense_operands(fmt, a, bt)
+    _check(load_library().odh_dense_fill(code, a.data_ptr(), bt.data_ptr(), m, n, k, _stream_ptr(a.device)))
+
+
+def dense_gemm(fmt, a, bt, out=None):
+    """``C[M,N] = A[M,K] · Bt[N,K]ᵀ`` on the FP16 (``v_mfma_f32_32x32x16_f16``, fp32 out) or INT8
+    (``v_mfma_i32_32x32x32_i8``, int32 out) matrix cores."""
+    import torch
+
+    code, m, n, k = _dense_operands(fmt, a, bt)
+    want = torch.int32 if code == ODH_DT_I8 else torch.float32
+    if out is None:
+        out = torch.empty((m, n), dtype=want, device=a.device)
+    elif tuple(out.shape) != (m, n) or out.dtype != want or not out.is_contiguous() or out.device != a.device:
+        raise ValueError(f"out must be a contiguous {want} [M,N] tensor on the operands' GPU")
+    _check(load_library().odh_dense_gemm(code, a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k,
+                                         _stream_ptr(a.device)))
+    return out
+
+
+def dense_verify(fmt, a, bt) -> dict:
+    """The fused check of the given operands against the closed form on a fresh counter block;
+    the kernel's time is taken with events around its one launch.  The dict of :func:`mx_verify`
+    (``tflops`` counts integer operations for ``"i8"``)."""
+    import torch
+
+    code, m, n, k = _dense_operands(fmt, a, bt)
+    dev = a.device
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
+        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load_library().odh_dense_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), m, n, k,
+                                                          tile_xcd.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    ms = e0.elapsed_time(e1)
+    return {
+        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
+        "ms": ms, "tflops": 2.0 * m * n * k / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
+    }
+
+
+def dense_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
+    """One FP16 / INT8 probe of a GPU: fill, then the GEMM with the check fused into its
+    epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
+    import torch
+
+    code = _dense_format(fmt)
+    if not dense_shape_ok(code, m, n, k):
+        raise ValueError("dense probe shape must be tile aligned")
+    dev = torch.device("cuda", device)
+    dtype = torch.int8 if code == ODH_DT_I8 else torch.float16
+    with torch.cuda.device(dev):
+        a = torch.empty((m, k), dtype=dtype, device=dev)
+        bt = torch.empty((n, k), dtype=dtype, device=dev)
+        dense_fill(code, a, bt)
+        return dense_verify(code, a, bt)
 
 
 class GpuProbe:
