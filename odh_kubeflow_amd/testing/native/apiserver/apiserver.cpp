@@ -34,7 +34,10 @@
 // object of its watch line and the body of the write's response, shared, not copied.  The
 // watch history is bounded per resource (--history events; a namespace's history is the
 // subsequence of its resource's, trimmed with it and dropped once empty and unwatched), so
-// memory does not grow with the number of namespaces.
+// memory does not grow with the number of namespaces.  The snapshots are copy-on-write trees
+// (json.hpp): a write starts from the stored version by reference and copies the path to what
+// it changes, consecutive versions share the rest, and validation, defaulting and the no-op
+// check skip what is still on the stored version's payload.
 //
 // Watch delivery: the committing thread delivers.  Once its commit has released the store lock
 // and its own request is answered, it writes the event to each live watcher whose namespace /
@@ -216,6 +219,11 @@ std::string mget(const Value& o, const char* k) {
   const Value* m = md(o);
   return m ? m->str_or(k) : "";
 }
+// the same without the copy: a view into `o`, for callers that only compare or look up
+std::string_view mview(const Value& o, const char* k) {
+  const Value* m = md(o);
+  return m ? m->sv(k) : std::string_view();
+}
 Value& mdm(Value& o) {
   Value& m = o["metadata"];
   if (!m.is_obj()) m = Value::object();
@@ -317,7 +325,7 @@ bool match_labels(const std::vector<LReq>& reqs, const Value& obj) {
   for (auto& r : reqs) {
     const Value* v = labels ? labels->get(r.key) : nullptr;
     bool has = v && v->is_str();
-    std::string s = has ? v->s : "";
+    std::string s = has ? std::string(v->s()) : std::string();
     if (r.op == "=") {
       if (!has || s != r.vals[0]) return false;
     } else if (r.op == "!=") {
@@ -358,7 +366,7 @@ std::vector<FReq> parse_fields(const std::string& text) {
 
 std::string scalar_str(const Value* v) {
   if (!v || v->is_null()) return "";
-  if (v->t == T::String) return v->s;
+  if (v->t == T::String) return std::string(v->s());
   if (v->t == T::Bool) return v->b ? "True" : "False";
   return kj::dump(*v);
 }
@@ -404,17 +412,19 @@ size_t ptr_index(const std::string& t) {
   return (size_t)std::stoul(t);
 }
 
+// the value at toks[0..upto) for writing: each level on the way down is detached (one copy of
+// that level's members when the document shares it), nothing beside the path
 Value* ptr_get(Value& doc, const std::vector<std::string>& toks, size_t upto) {
   Value* cur = &doc;
   for (size_t n = 0; n < upto; ++n) {
     const std::string& t = toks[n];
     if (cur->is_obj()) {
-      cur = cur->get(t);
+      cur = cur->get_mut(t);
       if (!cur) throw PatchErr{"path segment '" + t + "' not found"};
     } else if (cur->is_arr()) {
       size_t idx = ptr_index(t);
-      if (idx >= cur->arr.size()) throw PatchErr{"bad list index " + t};
-      cur = &cur->arr[idx];
+      if (idx >= cur->arr().size()) throw PatchErr{"bad list index " + t};
+      cur = &cur->arr_mut()[idx];
     } else {
       throw PatchErr{"cannot traverse into scalar"};
     }
@@ -433,11 +443,12 @@ void ptr_add(Value& doc, const std::vector<std::string>& toks, Value v) {
     (*parent)[last] = std::move(v);
   } else if (parent->is_arr()) {
     if (last == "-") {
-      parent->arr.push_back(std::move(v));
+      parent->arr_mut().push_back(std::move(v));
     } else {
       size_t idx = ptr_index(last);
-      if (idx > parent->arr.size()) throw PatchErr{"list index out of range"};
-      parent->arr.insert(parent->arr.begin() + idx, std::move(v));
+      if (idx > parent->arr().size()) throw PatchErr{"list index out of range"};
+      auto& a = parent->arr_mut();
+      a.insert(a.begin() + idx, std::move(v));
     }
   } else {
     throw PatchErr{"cannot add into scalar"};
@@ -449,17 +460,18 @@ Value ptr_remove(Value& doc, const std::vector<std::string>& toks) {
   Value* parent = ptr_get(doc, toks, toks.size() - 1);
   const std::string& last = toks.back();
   if (parent->is_obj()) {
-    Value* v = parent->get(last);
+    const Value* v = parent->get(last);
     if (!v) throw PatchErr{"remove: '" + last + "' not found"};
-    Value out = std::move(*v);
+    Value out = *v;
     parent->erase(last);
     return out;
   }
   if (parent->is_arr()) {
     size_t idx = ptr_index(last);
-    if (idx >= parent->arr.size()) throw PatchErr{"remove: bad index"};
-    Value out = std::move(parent->arr[idx]);
-    parent->arr.erase(parent->arr.begin() + idx);
+    if (idx >= parent->arr().size()) throw PatchErr{"remove: bad index"};
+    auto& a = parent->arr_mut();
+    Value out = std::move(a[idx]);
+    a.erase(a.begin() + idx);
     return out;
   }
   throw PatchErr{"cannot remove from scalar"};
@@ -467,7 +479,7 @@ Value ptr_remove(Value& doc, const std::vector<std::string>& toks) {
 
 Value apply_json_patch(Value doc, const Value& ops) {
   if (!ops.is_arr()) throw PatchErr{"JSON patch must be an array"};
-  for (auto& op : ops.arr) {
+  for (auto& op : ops.arr()) {
     std::string kind = op.str_or("op");
     auto toks = ptr_tokens(op.str_or("path"));
     const Value* val = op.get("value");
@@ -487,7 +499,7 @@ Value apply_json_patch(Value doc, const Value& ops) {
       ptr_add(doc, toks, std::move(v));
     } else if (kind == "copy") {
       auto ft = ptr_tokens(op.str_or("from"));
-      Value v = *ptr_get(doc, ft, ft.size());
+      Value v = *ptr_get(doc, ft, ft.size());  // shares the subtree: both places hold one payload
       ptr_add(doc, toks, std::move(v));
     } else if (kind == "test") {
       if (!(*ptr_get(doc, toks, toks.size()) == (val ? *val : Value())))
@@ -506,10 +518,15 @@ void merge_patch_in(Value& target, const Value& patch) {
     return;
   }
   if (!target.is_obj()) target = Value::object();
-  for (auto& m : patch.obj) {
-    if (m.v.is_null()) target.erase(m.k);
-    else if (m.v.is_obj()) merge_patch_in(target[m.k], m.v);
-    else target[m.k] = m.v;
+  for (auto& m : patch.obj()) {
+    if (m.v.is_null()) {
+      target.erase(m.k);
+    } else if (m.v.is_obj()) {
+      merge_patch_in(target[m.k], m.v);
+    } else {
+      const Value* have = target.get(m.k);
+      if (!have || !have->same(m.v)) target[m.k] = m.v;
+    }
   }
 }
 
@@ -520,7 +537,7 @@ Value merge_patch(const Value& target, const Value& patch) {
   return out;
 }
 
-const char* smp_key(const std::string& field, bool* known) {
+const char* smp_key(std::string_view field, bool* known) {
   static const std::pair<const char*, const char*> keys[] = {
       {"containers", "name"}, {"initContainers", "name"}, {"ephemeralContainers", "name"}, {"env", "name"},
       {"volumes", "name"},    {"volumeMounts", "mountPath"}, {"ports", "containerPort"}, {"imagePullSecrets", "name"},
@@ -537,7 +554,7 @@ const char* smp_key(const std::string& field, bool* known) {
 Value strategic_patch(const Value& target, const Value& patch) {
   if (!patch.is_obj()) return patch;
   Value out = target.is_obj() ? target : Value::object();
-  for (auto& m : patch.obj) {
+  for (auto& m : patch.obj()) {
     if (!m.k.empty() && m.k[0] == '$') continue;
     bool known;
     const char* key = smp_key(m.k, &known);
@@ -548,26 +565,27 @@ Value strategic_patch(const Value& target, const Value& patch) {
       out[m.k] = strategic_patch(cur ? *cur : Value(), m.v);
     } else if (m.v.is_arr() && key && cur && cur->is_arr()) {
       Value merged = *cur;
-      for (auto& item : m.v.arr) {
+      auto& ma = merged.arr_mut();  // the list's own level; its items stay shared until patched
+      for (auto& item : m.v.arr()) {
         const Value* kv = item.is_obj() ? item.get(key) : nullptr;
         if (!kv) {
-          merged.arr.push_back(item);
+          ma.push_back(item);
           continue;
         }
         int idx = -1;
-        for (size_t n = 0; n < merged.arr.size(); ++n) {
-          const Value* ek = merged.arr[n].is_obj() ? merged.arr[n].get(key) : nullptr;
+        for (size_t n = 0; n < ma.size(); ++n) {
+          const Value* ek = ma[n].is_obj() ? ma[n].get(key) : nullptr;
           if (ek && *ek == *kv) {
             idx = (int)n;
             break;
           }
         }
         if (item.str_or("$patch") == "delete") {
-          if (idx >= 0) merged.arr.erase(merged.arr.begin() + idx);
+          if (idx >= 0) ma.erase(ma.begin() + idx);
           continue;
         }
-        if (idx < 0) merged.arr.push_back(item);
-        else merged.arr[idx] = strategic_patch(merged.arr[idx], item);
+        if (idx < 0) ma.push_back(item);
+        else ma[idx] = strategic_patch(ma[idx], item);
       }
       out[m.k] = std::move(merged);
     } else {
@@ -896,7 +914,7 @@ void index_owner(const Res& r, const Value& o, bool remove) {
   const Value* refs = m ? m->get("ownerReferences") : nullptr;
   if (!refs || !refs->is_arr()) return;
   auto k = std::make_tuple(r.key, mget(o, "namespace"), mget(o, "name"));
-  for (auto& ref : refs->arr) {
+  for (auto& ref : refs->arr()) {
     std::string u = ref.str_or("uid");
     if (u.empty()) continue;
     IdxStripe& st = idx(u);
@@ -913,13 +931,12 @@ void index_owner(const Res& r, const Value& o, bool remove) {
   }
 }
 
-// callers hold the resource's store lock
-void emit(const Res& r, const char* type, Obj obj, Obj old) {
+// callers hold the resource's store lock; `rv` is the resourceVersion they have just given `obj`
+void emit(const Res& r, const char* type, Obj obj, Obj old, int64_t rv) {
   Bucket& b = bucket(r);
   std::lock_guard<std::mutex> hg(b.hmu);
   const std::string evns = mget(*obj, "namespace");
-  Ev e{++b.all.seq, std::stoll(mget(*obj, "resourceVersion")), type, std::move(obj), std::move(old),
-       std::make_shared<EvCache>()};
+  Ev e{++b.all.seq, rv, type, std::move(obj), std::move(old), std::make_shared<EvCache>()};
   if (!evns.empty()) {
     Hist& h = b.by_ns[evns];
     Ev copy = e;  // the same event (shared object, old object and serialisation cache)
@@ -932,8 +949,9 @@ void emit(const Res& r, const char* type, Obj obj, Obj old) {
     // history holds at most --history events per resource however many namespaces there are
     const Ev& old = b.all.hist.front();
     b.dropped_rv = old.rv;
-    const std::string ons = mget(*old.obj, "namespace");
-    if (!ons.empty()) {
+    const std::string_view onv = mview(*old.obj, "namespace");
+    if (!onv.empty()) {
+      const std::string ons(onv);
       auto it = b.by_ns.find(ons);
       if (it != b.by_ns.end() && !it->second.hist.empty() && it->second.hist.front().rv == old.rv) {
         t_free.push_back(std::move(it->second.hist.front()));
@@ -981,9 +999,8 @@ void emit(const Res& r, const char* type, Obj obj, Obj old) {
     auto rg = b.watchers.equal_range(ns);
     for (auto it = rg.first; it != rg.second; ++it) t_wake.push_back({it->second, ev.obj, ev.old, false});
   };
-  const std::string ns = mget(*ev.obj, "namespace");
-  wake(ns);
-  if (!ns.empty()) wake("");
+  wake(evns);
+  if (!evns.empty()) wake("");
 }
 
 // `o` as the requested API version: a non-storage version differs in apiVersion only, so it
@@ -995,19 +1012,20 @@ void dump_version(std::string& out, const Res& r, const Value& o, const std::str
 
 // a and b agree on every member not named in skip (object members in any order); no copies
 bool members_equal_except(const Value& a, const Value& b, std::initializer_list<const char*> skip) {
-  auto skipped = [&](const std::string& k) {
+  if (a.same(b)) return true;
+  auto skipped = [&](std::string_view k) {
     for (const char* x : skip)
       if (k == x) return true;
     return false;
   };
   size_t na = 0, nb = 0;
-  for (auto& m : a.obj) {
+  for (auto& m : a.obj()) {
     if (skipped(m.k)) continue;
     ++na;
     const Value* o = b.get(m.k);
     if (!o || !(m.v == *o)) return false;
   }
-  for (auto& m : b.obj)
+  for (auto& m : b.obj())
     if (!skipped(m.k)) ++nb;
   return na == nb;
 }
@@ -1057,7 +1075,7 @@ const char* type_name(const Value& v) {
 
 std::string fmt_val(const Value& v) {
   switch (v.t) {
-    case T::String: return "\"" + v.s + "\"";
+    case T::String: return "\"" + std::string(v.s()) + "\"";
     case T::Bool: return v.b ? "true" : "false";
     case T::Int: return std::to_string(v.i);
     case T::Double: {
@@ -1075,64 +1093,19 @@ bool schema_flag(const Value& s, const char* k) {
   return v && v->t == T::Bool && v->b;
 }
 
+// a schema's string member as a view ("" when absent): read per node, never copied
+std::string_view schema_str(const Value& s, const char* k) {
+  const Value* v = s.get(k);
+  return v && v->is_str() ? v->s() : std::string_view();
+}
+
 bool type_ok(const Value& s, const Value& v) {
   if (schema_flag(s, "x-kubernetes-int-or-string")) return v.t == T::Int || v.t == T::String;
-  std::string t = s.str_or("type");
+  const std::string_view t = schema_str(s, "type");
   if (t.empty()) return true;
   if (t == "integer") return v.t == T::Int || (v.t == T::Double && v.d == (double)(int64_t)v.d);
   if (t == "number") return v.t == T::Int || v.t == T::Double;
   return t == type_name(v);
-}
-
-void schema_prune(const Value& s, Value& v, bool root) {
-  if (v.is_obj()) {
-    if (schema_flag(s, "x-kubernetes-preserve-unknown-fields")) return;
-    const Value* props = s.get("properties");
-    const Value* addl = s.get("additionalProperties");
-    bool addl_true = addl && addl->t == T::Bool && addl->b;
-    for (size_t n = 0; n < v.obj.size();) {
-      kj::Member& m = v.obj[n];
-      if (root && (m.k == "apiVersion" || m.k == "kind" || m.k == "metadata")) {
-        ++n;
-        continue;
-      }
-      const Value* sub = props ? props->get(m.k) : nullptr;
-      if (!sub && addl && addl->is_obj()) sub = addl;
-      if (!sub) {
-        if (!addl_true) {
-          v.obj.erase(v.obj.begin() + n);
-          continue;
-        }
-        ++n;
-        continue;
-      }
-      if (m.v.is_null() && !schema_flag(*sub, "nullable")) {
-        v.obj.erase(v.obj.begin() + n);
-        continue;
-      }
-      schema_prune(*sub, m.v, false);
-      ++n;
-    }
-  } else if (v.is_arr()) {
-    if (const Value* item = s.get("items"); item && item->is_obj())
-      for (auto& x : v.arr) schema_prune(*item, x, false);
-  }
-}
-
-void schema_default(const Value& s, Value& v) {
-  if (v.is_obj()) {
-    if (const Value* props = s.get("properties"); props && props->is_obj())
-      for (auto& p : props->obj) {
-        if (!v.get(p.k))
-          if (const Value* d = p.v.get("default")) v[p.k] = *d;
-        if (Value* x = v.get(p.k)) schema_default(p.v, *x);
-      }
-    if (const Value* addl = s.get("additionalProperties"); addl && addl->is_obj())
-      for (auto& m : v.obj) schema_default(*addl, m.v);
-  } else if (v.is_arr()) {
-    if (const Value* item = s.get("items"); item && item->is_obj())
-      for (auto& x : v.arr) schema_default(*item, x);
-  }
 }
 
 const std::regex& cached_regex(const std::string& pat) {
@@ -1144,88 +1117,239 @@ const std::regex& cached_regex(const std::string& pat) {
   return *slot;
 }
 
-void schema_validate(const Value& s, const Value& v, const std::string& path, std::vector<std::string>& errs) {
-  if (!type_ok(s, v)) {
-    std::string want = schema_flag(s, "x-kubernetes-int-or-string") ? "integer or string" : s.str_or("type");
-    errs.push_back(path + ": Invalid value: " + fmt_val(v) + ": " + path + " in body must be of type " + want + ": \"" +
-                   type_name(v) + "\"");
-    return;
-  }
-  std::string fmt = s.str_or("format");
-  if ((fmt == "int32") && v.t == T::Int && (v.i < INT32_MIN || v.i > INT32_MAX))
-    errs.push_back(path + ": Invalid value: " + std::to_string(v.i) + ": " + path + " in body should be a valid int32");
-  if (const Value* en = s.get("enum"); en && en->is_arr()) {
-    bool ok = false;
-    for (auto& x : en->arr) ok = ok || x == v;
-    if (!ok) {
-      std::string l;
-      for (auto& x : en->arr) l += (l.empty() ? "" : ", ") + fmt_val(x);
-      errs.push_back(path + ": Unsupported value: " + fmt_val(v) + ": supported values: " + l);
-    }
-  }
-  if (const Value* pat = s.get("pattern"); pat && pat->is_str() && v.is_str())
-    if (!std::regex_search(v.s, cached_regex(pat->s)))
-      errs.push_back(path + ": Invalid value: " + fmt_val(v) + ": " + path + " in body should match '" + pat->s + "'");
-  if (v.is_obj()) {
-    const Value* props = s.get("properties");
-    if (const Value* req = s.get("required"); req && req->is_arr())
-      for (auto& r : req->arr)
-        if (r.is_str() && !v.get(r.s)) errs.push_back((path.empty() ? "" : path + ".") + r.s + ": Required value");
-    const Value* addl = s.get("additionalProperties");
-    for (auto& m : v.obj) {
-      const Value* sub = props ? props->get(m.k) : nullptr;
-      if (!sub && addl && addl->is_obj()) sub = addl;
-      if (sub && !(path.empty() && m.k == "metadata")) schema_validate(*sub, m.v, path.empty() ? m.k : path + "." + m.k, errs);
-    }
-  } else if (v.is_arr()) {
-    if (const Value* mi = s.get("minItems"); mi && mi->t == T::Int && (int64_t)v.arr.size() < mi->i)
-      errs.push_back(path + ": Invalid value: " + std::to_string(v.arr.size()) + ": " + path + " in body should have at least " +
-                     std::to_string(mi->i) + " items");
-    if (const Value* ma = s.get("maxItems"); ma && ma->t == T::Int && (int64_t)v.arr.size() > ma->i)
-      errs.push_back(path + ": Too many: " + std::to_string(v.arr.size()) + ": must have at most " + std::to_string(ma->i) + " items");
-    std::string lt = s.str_or("x-kubernetes-list-type");
-    if (lt == "set") {
-      for (size_t i = 0; i < v.arr.size(); ++i)
-        for (size_t j = 0; j < i; ++j)
-          if (v.arr[j] == v.arr[i]) {
-            errs.push_back(path + "[" + std::to_string(i) + "]: Duplicate value: " + fmt_val(v.arr[i]));
-            break;
-          }
-    } else if (lt == "map") {
-      const Value* keys = s.get("x-kubernetes-list-map-keys");
-      for (size_t i = 0; keys && keys->is_arr() && i < v.arr.size(); ++i)
-        for (size_t j = 0; j < i; ++j) {
-          bool same = v.arr[i].is_obj() && v.arr[j].is_obj();
-          for (auto& k : keys->arr) {
-            if (!same) break;
-            const Value* a = v.arr[i].get(k.s);
-            const Value* b = v.arr[j].get(k.s);
-            same = (!a && !b) || (a && b && *a == *b);
-          }
-          if (same) {
-            std::string d;
-            for (auto& k : keys->arr) {
-              const Value* a = v.arr[i].get(k.s);
-              d += (d.empty() ? "" : ", ") + std::string("\"") + k.s + "\":" + (a ? fmt_val(*a) : "null");
-            }
-            errs.push_back(path + "[" + std::to_string(i) + "]: Duplicate value: {" + d + "}");
-            break;
-          }
-        }
-    }
-    if (const Value* item = s.get("items"); item && item->is_obj())
-      for (size_t i = 0; i < v.arr.size(); ++i) schema_validate(*item, v.arr[i], path + "[" + std::to_string(i) + "]", errs);
-  }
+// Where the walk stands, as a chain through its own stack frames: the dotted path is only
+// written out when an error is reported.
+struct VPath {
+  const VPath* up;
+  std::string_view key;
+  size_t idx;
+  bool is_idx;
+};
+std::string path_str(const VPath* p) {
+  if (!p) return "";
+  std::string s = path_str(p->up);
+  if (p->is_idx) return s + "[" + std::to_string(p->idx) + "]";
+  return s.empty() ? std::string(p->key) : s + "." + std::string(p->key);
 }
 
-std::optional<std::string> validate(const Res& r, Value& o) {
+// What a walk does at a node.  Pruning stops below x-kubernetes-preserve-unknown-fields, below
+// the root's apiVersion / kind / metadata and inside an inserted default; the root's metadata is
+// not checked.
+constexpr int W_PRUNE = 1, W_DEFAULT = 2, W_CHECK = 4, W_ALL = 7;
+
+// Prune, default and check `v` against `s` in one walk: at each node its own level is pruned
+// and defaulted, then checked, then its children are walked, which reports the same errors in
+// the same order as three walks of the whole object did.  `v` is only read: a node that has to
+// change is rebuilt (one level copied, the rest shared) and handed back in `out`, the return
+// value saying so; nearly every write changes nothing here.
+//
+// `old` is the value at the same place in the version this write replaces (nullptr: none).  A
+// node on the same payload as `old` is not walked at all: the stored version went through this
+// walk against the same schema node when it was written — schemas are read once, before the
+// server listens (load_config), and g_schemas never changes afterwards, so a place in a
+// resource's objects always meets the same schema node — and nothing a node is checked for
+// depends on anything outside it.  So a status write walks the status, not the spec.
+bool schema_walk(const Value& s, const Value& v, const Value* old, int fl, bool root, const VPath* path,
+                 std::vector<std::string>& errs, Value& out) {
+  if (old && v.same(*old)) return false;
+  const bool container = v.is_obj() || v.is_arr();
+  if ((fl & W_CHECK) && (fl & (W_PRUNE | W_DEFAULT)) && container) {
+    // enum and the set / map list types compare whole subtrees: those are pruned and defaulted
+    // to the bottom first, then checked
+    const Value* en = s.get("enum");
+    bool deep = en && en->is_arr();
+    if (!deep && v.is_arr()) {
+      const std::string_view lt = schema_str(s, "x-kubernetes-list-type");
+      deep = lt == "set" || lt == "map";
+    }
+    if (deep) {
+      std::vector<std::string> none;
+      Value fixed, unused;
+      const bool changed = schema_walk(s, v, old, fl & ~W_CHECK, root, path, none, fixed);
+      schema_walk(s, changed ? fixed : v, old, W_CHECK, root, path, errs, unused);
+      if (changed) out = std::move(fixed);
+      return changed;
+    }
+  }
+  if (fl & W_CHECK) {
+    if (!type_ok(s, v)) {
+      const std::string p = path_str(path);
+      const std::string want(schema_flag(s, "x-kubernetes-int-or-string") ? std::string_view("integer or string") : schema_str(s, "type"));
+      errs.push_back(p + ": Invalid value: " + fmt_val(v) + ": " + p + " in body must be of type " + want + ": \"" +
+                     type_name(v) + "\"");
+      return false;
+    }
+    if (v.t == T::Int && (v.i < INT32_MIN || v.i > INT32_MAX) && schema_str(s, "format") == "int32") {
+      const std::string p = path_str(path);
+      errs.push_back(p + ": Invalid value: " + std::to_string(v.i) + ": " + p + " in body should be a valid int32");
+    }
+    if (const Value* en = s.get("enum"); en && en->is_arr()) {
+      bool ok = false;
+      for (auto& x : en->arr()) ok = ok || x == v;
+      if (!ok) {
+        std::string l;
+        for (auto& x : en->arr()) l += (l.empty() ? "" : ", ") + fmt_val(x);
+        errs.push_back(path_str(path) + ": Unsupported value: " + fmt_val(v) + ": supported values: " + l);
+      }
+    }
+    if (v.is_str())
+      if (const Value* pat = s.get("pattern"); pat && pat->is_str())
+        if (!std::regex_search(v.s().begin(), v.s().end(), cached_regex(std::string(pat->s())))) {
+          const std::string p = path_str(path);
+          errs.push_back(p + ": Invalid value: " + fmt_val(v) + ": " + p + " in body should match '" + std::string(pat->s()) + "'");
+        }
+  }
+  if (v.is_obj()) {
+    if ((fl & W_PRUNE) && schema_flag(s, "x-kubernetes-preserve-unknown-fields")) fl &= ~W_PRUNE;
+    const Value* props = s.get("properties");
+    const Value* addl = s.get("additionalProperties");
+    const bool addl_obj = addl && addl->is_obj();
+    const bool addl_true = addl && addl->t == T::Bool && addl->b;
+    Value nv;
+    bool mine = false;
+    auto own = [&]() -> std::vector<kj::Member>& {
+      if (!mine) {
+        nv = v;
+        mine = true;
+      }
+      return nv.obj_mut();
+    };
+    auto cur = [&]() -> const std::vector<kj::Member>& { return mine ? nv.obj() : v.obj(); };
+    if (fl & W_PRUNE) {
+      const auto& ms = v.obj();
+      size_t removed = 0;
+      for (size_t n = 0; n < ms.size(); ++n) {
+        const kj::Member& m = ms[n];
+        if (root && (m.k == "apiVersion" || m.k == "kind" || m.k == "metadata")) continue;
+        const Value* sub = props ? props->get(m.k) : nullptr;
+        if (!sub && addl_obj) sub = addl;
+        const bool drop = sub ? m.v.is_null() && !schema_flag(*sub, "nullable") : !addl_true;
+        if (drop) {
+          auto& o = own();
+          o.erase(o.begin() + (n - removed));
+          ++removed;
+        }
+      }
+    }
+    const size_t n_own = cur().size();  // members from here on are defaults put in below: not pruned
+    if ((fl & W_DEFAULT) && props && props->is_obj())
+      for (auto& p : props->obj()) {
+        bool have = false;
+        for (auto& m : cur()) have = have || m.k == p.k;
+        if (!have)
+          if (const Value* d = p.v.get("default")) own().push_back(kj::Member{p.k, *d});
+      }
+    if (fl & W_CHECK)
+      if (const Value* req = s.get("required"); req && req->is_arr())
+        for (auto& r : req->arr()) {
+          if (!r.is_str()) continue;
+          bool have = false;
+          for (auto& m : cur()) have = have || m.k == std::string_view(r.s());
+          if (!have) {
+            const std::string p = path_str(path);
+            errs.push_back((p.empty() ? "" : p + ".") + std::string(r.s()) + ": Required value");
+          }
+        }
+    for (size_t n = 0; n < cur().size(); ++n) {
+      const kj::Key& k = cur()[n].k;  // stays put: own() copies the members, it never moves them
+      int cf = fl;
+      if (n >= n_own) cf &= ~W_PRUNE;
+      if (root && k == "metadata") cf &= ~(W_PRUNE | W_CHECK);
+      else if (root && (k == "apiVersion" || k == "kind")) cf &= ~W_PRUNE;
+      const Value* psub = props ? props->get(k) : nullptr;
+      const Value* sub = psub ? psub : (addl_obj ? addl : nullptr);
+      if (!sub) continue;
+      const Value* co = old && old->is_obj() ? old->get(k) : nullptr;
+      const VPath cp{path, k.sv(), 0, false};
+      if (cf) {
+        Value changed;
+        const Value& child = cur()[n].v;
+        if (schema_walk(*sub, child, co, cf, false, &cp, errs, changed)) own()[n].v = std::move(changed);
+      }
+      if (psub && addl_obj && (fl & W_DEFAULT)) {
+        // a schema with properties AND an additionalProperties schema defaults a named member
+        // against both (structural schemas do not allow the pair; kept as it was)
+        std::vector<std::string> none;
+        Value changed;
+        const Value& child = cur()[n].v;
+        if (schema_walk(*addl, child, nullptr, W_DEFAULT, false, &cp, none, changed)) own()[n].v = std::move(changed);
+      }
+    }
+    if (mine) out = std::move(nv);
+    return mine;
+  }
+  if (v.is_arr()) {
+    const auto& a = v.arr();
+    if (fl & W_CHECK) {
+      if (const Value* mi = s.get("minItems"); mi && mi->t == T::Int && (int64_t)a.size() < mi->i) {
+        const std::string p = path_str(path);
+        errs.push_back(p + ": Invalid value: " + std::to_string(a.size()) + ": " + p + " in body should have at least " +
+                       std::to_string(mi->i) + " items");
+      }
+      if (const Value* ma = s.get("maxItems"); ma && ma->t == T::Int && (int64_t)a.size() > ma->i)
+        errs.push_back(path_str(path) + ": Too many: " + std::to_string(a.size()) + ": must have at most " +
+                       std::to_string(ma->i) + " items");
+      const std::string_view lt = schema_str(s, "x-kubernetes-list-type");
+      if (lt == "set") {
+        for (size_t i = 0; i < a.size(); ++i)
+          for (size_t j = 0; j < i; ++j)
+            if (a[j] == a[i]) {
+              errs.push_back(path_str(path) + "[" + std::to_string(i) + "]: Duplicate value: " + fmt_val(a[i]));
+              break;
+            }
+      } else if (lt == "map") {
+        const Value* keys = s.get("x-kubernetes-list-map-keys");
+        for (size_t i = 0; keys && keys->is_arr() && i < a.size(); ++i)
+          for (size_t j = 0; j < i; ++j) {
+            bool same = a[i].is_obj() && a[j].is_obj();
+            for (auto& k : keys->arr()) {
+              if (!same) break;
+              const Value* x = a[i].get(k.s());
+              const Value* y = a[j].get(k.s());
+              same = (!x && !y) || (x && y && *x == *y);
+            }
+            if (same) {
+              std::string d;
+              for (auto& k : keys->arr()) {
+                const Value* x = a[i].get(k.s());
+                d += (d.empty() ? "" : ", ") + std::string("\"") + std::string(k.s()) + "\":" + (x ? fmt_val(*x) : "null");
+              }
+              errs.push_back(path_str(path) + "[" + std::to_string(i) + "]: Duplicate value: {" + d + "}");
+              break;
+            }
+          }
+      }
+    }
+    const Value* item = s.get("items");
+    if (!item || !item->is_obj()) return false;
+    Value nv;
+    bool mine = false;
+    for (size_t n = 0; n < a.size(); ++n) {
+      const Value* co = old && old->is_arr() && n < old->arr().size() ? &old->arr()[n] : nullptr;
+      const VPath cp{path, {}, n, true};
+      Value changed;
+      if (schema_walk(*item, a[n], co, fl, false, &cp, errs, changed)) {
+        if (!mine) {
+          nv = v;
+          mine = true;
+        }
+        nv.arr_mut()[n] = std::move(changed);
+      }
+    }
+    if (mine) out = std::move(nv);
+    return mine;
+  }
+  return false;
+}
+
+// `old`: the stored version this write replaces (nullptr for a create)
+std::optional<std::string> validate(const Res& r, Value& o, const Value* old) {
   PhaseTimer pt(PH_VALIDATE);
   auto it = g_schemas.find(r.key);
   if (it == g_schemas.end()) return std::nullopt;
-  schema_prune(it->second, o, true);
-  schema_default(it->second, o);
   std::vector<std::string> errs;
-  schema_validate(it->second, o, "", errs);
+  Value out;
+  if (schema_walk(it->second, o, old, W_ALL, true, nullptr, errs, out)) o = std::move(out);
   if (errs.empty()) return std::nullopt;
   if (errs.size() == 1) return errs[0];
   std::string all = "[";
@@ -1238,7 +1362,7 @@ std::optional<std::string> validate(const Res& r, Value& o) {
 // resource.Quantity canonicalisation), applied to every Pod / StatefulSet / Deployment /
 // Service write so controllers see the live objects a real apiserver would hand them.
 
-void set_default(Value& o, const char* k, Value v) {
+void set_default(Value& o, std::string_view k, Value v) {
   if (!o.get(k)) o[k] = std::move(v);
 }
 
@@ -1348,11 +1472,12 @@ std::string canon_quantity(const std::string& text) {
 
 void canon_quantities(Value* q) {
   if (!q || !q->is_obj()) return;
-  for (auto& m : q->obj)
-    if (m.v.is_str()) {
-      std::string c = canon_quantity(m.v.s);
-      if (!c.empty()) m.v.s = c;
-    }
+  for (size_t n = 0; n < q->obj().size(); ++n) {
+    const Value& v = q->obj()[n].v;
+    if (!v.is_str()) continue;
+    std::string c = canon_quantity(std::string(v.s()));
+    if (!c.empty() && c != v.s()) q->obj_mut()[n].v = Value::str(std::move(c));
+  }
 }
 
 std::string image_pull_policy(const std::string& image) {
@@ -1369,7 +1494,7 @@ void default_probe(Value* p) {
   set_default(*p, "periodSeconds", Value::integer(10));
   set_default(*p, "successThreshold", Value::integer(1));
   set_default(*p, "failureThreshold", Value::integer(3));
-  if (Value* hg = p->get("httpGet"); hg && hg->is_obj()) {
+  if (Value* hg = p->get_mut("httpGet"); hg && hg->is_obj()) {
     set_default(*hg, "path", Value::str("/"));
     set_default(*hg, "scheme", Value::str("HTTP"));
   }
@@ -1379,20 +1504,20 @@ void default_container(Value& c) {
   if (!c.is_obj()) return;
   set_default(c, "terminationMessagePath", Value::str("/dev/termination-log"));
   set_default(c, "terminationMessagePolicy", Value::str("File"));
-  if (const Value* img = c.get("image"); img && img->is_str()) set_default(c, "imagePullPolicy", Value::str(image_pull_policy(img->s)));
-  if (Value* ports = c.get("ports"); ports && ports->is_arr())
-    for (auto& p : ports->arr)
+  if (const Value* img = c.get("image"); img && img->is_str()) set_default(c, "imagePullPolicy", Value::str(image_pull_policy(std::string(img->s()))));
+  if (Value* ports = c.get_mut("ports"); ports && ports->is_arr())
+    for (auto& p : ports->arr_mut())
       if (p.is_obj()) set_default(p, "protocol", Value::str("TCP"));
-  if (Value* env = c.get("env"); env && env->is_arr())
-    for (auto& e : env->arr) {
-      Value* vf = e.get("valueFrom");
-      Value* fr = vf ? vf->get("fieldRef") : nullptr;
+  if (Value* env = c.get_mut("env"); env && env->is_arr())
+    for (auto& e : env->arr_mut()) {
+      Value* vf = e.get_mut("valueFrom");
+      Value* fr = vf ? vf->get_mut("fieldRef") : nullptr;
       if (fr && fr->is_obj()) set_default(*fr, "apiVersion", Value::str("v1"));
     }
   Value& res = obj_at(c, "resources");
-  canon_quantities(res.get("limits"));
-  canon_quantities(res.get("requests"));
-  for (const char* k : {"livenessProbe", "readinessProbe", "startupProbe"}) default_probe(c.get(k));
+  canon_quantities(res.get_mut("limits"));
+  canon_quantities(res.get_mut("requests"));
+  for (const char* k : {"livenessProbe", "readinessProbe", "startupProbe"}) default_probe(c.get_mut(k));
 }
 
 void default_pod_spec(Value& spec) {
@@ -1405,18 +1530,18 @@ void default_pod_spec(Value& spec) {
   if (!spec.str_or("serviceAccountName").empty() && spec.str_or("serviceAccount").empty())
     spec["serviceAccount"] = Value::str(spec.str_or("serviceAccountName"));
   for (const char* k : {"initContainers", "containers"})
-    if (Value* cs = spec.get(k); cs && cs->is_arr())
-      for (auto& c : cs->arr) default_container(c);
-  if (Value* vols = spec.get("volumes"); vols && vols->is_arr())
-    for (auto& v : vols->arr) {
+    if (Value* cs = spec.get_mut(k); cs && cs->is_arr())
+      for (auto& c : cs->arr_mut()) default_container(c);
+  if (Value* vols = spec.get_mut("volumes"); vols && vols->is_arr())
+    for (auto& v : vols->arr_mut()) {
       if (!v.is_obj()) continue;
       for (const char* src : {"secret", "configMap"})
-        if (Value* x = v.get(src); x && x->is_obj()) set_default(*x, "defaultMode", Value::integer(420));
-      if (Value* hp = v.get("hostPath"); hp && hp->is_obj()) set_default(*hp, "type", Value::str(""));
-      if (Value* ed = v.get("emptyDir"); ed && ed->is_obj())
-        if (Value* sl = ed->get("sizeLimit"); sl && sl->is_str()) {
-          std::string c = canon_quantity(sl->s);
-          if (!c.empty()) sl->s = c;
+        if (Value* x = v.get_mut(src); x && x->is_obj()) set_default(*x, "defaultMode", Value::integer(420));
+      if (Value* hp = v.get_mut("hostPath"); hp && hp->is_obj()) set_default(*hp, "type", Value::str(""));
+      if (Value* ed = v.get_mut("emptyDir"); ed && ed->is_obj())
+        if (Value* sl = ed->get_mut("sizeLimit"); sl && sl->is_str()) {
+          std::string c = canon_quantity(std::string(sl->s()));
+          if (!c.empty() && c != sl->s()) *sl = Value::str(std::move(c));
         }
     }
 }
@@ -1455,13 +1580,14 @@ void api_defaults(const Res& r, Value& o) {
   } else if (r.key == "pods") {
     Value& spec = obj_at(o, "spec");
     for (const char* k : {"containers", "initContainers"})
-      if (Value* cs = spec.get(k); cs && cs->is_arr())
-        for (auto& c : cs->arr) {
-          Value* res = c.get("resources");
-          Value* lim = res ? res->get("limits") : nullptr;
-          if (!lim || !lim->is_obj() || lim->obj.empty()) continue;
+      if (Value* cs = spec.get_mut(k); cs && cs->is_arr())
+        for (auto& c : cs->arr_mut()) {
+          Value* res = c.get_mut("resources");
+          const Value* lp = res ? res->get("limits") : nullptr;
+          if (!lp || !lp->is_obj() || lp->obj().empty()) continue;
+          const Value lim = *lp;  // held: adding "requests" may move the members of `res`
           Value& req = obj_at(*res, "requests");
-          for (auto& m : lim->obj) set_default(req, m.k.c_str(), m.v);
+          for (auto& m : lim.obj()) set_default(req, m.k.sv(), m.v);
         }
     default_pod_spec(spec);
   } else if (r.key == "services") {
@@ -1471,13 +1597,13 @@ void api_defaults(const Res& r, Value& o) {
     std::string type = spec.str_or("type");
     if ((type == "ClusterIP" || type == "NodePort" || type == "LoadBalancer") && spec.str_or("clusterIP") != "None") {
       Value fam = Value::array();
-      fam.arr.push_back(Value::str("IPv4"));
+      fam.arr_mut().push_back(Value::str("IPv4"));
       set_default(spec, "ipFamilies", fam);
       set_default(spec, "ipFamilyPolicy", Value::str("SingleStack"));
       set_default(spec, "internalTrafficPolicy", Value::str("Cluster"));
     }
-    if (Value* ports = spec.get("ports"); ports && ports->is_arr())
-      for (auto& p : ports->arr) {
+    if (Value* ports = spec.get_mut("ports"); ports && ports->is_arr())
+      for (auto& p : ports->arr_mut()) {
         if (!p.is_obj()) continue;
         set_default(p, "protocol", Value::str("TCP"));
         const Value* tp = p.get("targetPort");
@@ -1504,7 +1630,7 @@ void defaults(const Res& r, Value& o, bool api = true) {
       snprintf(ip, sizeof(ip), "10.96.%d.%d", (int)((rvnow >> 8) & 255), (int)((rvnow & 255) ? (rvnow & 255) : 1));
       spec["clusterIP"] = Value::str(ip);
       Value ips = Value::array();
-      ips.arr.push_back(Value::str(ip));
+      ips.arr_mut().push_back(Value::str(ip));
       spec["clusterIPs"] = ips;
     }
   } else if (r.key == "namespaces") {
@@ -1711,15 +1837,15 @@ std::vector<LReq> selector_reqs(const Value& sel) {
   std::vector<LReq> out;
   if (const Value* ml = sel.get("matchLabels"))
     if (ml->is_obj())
-      for (auto& kv : ml->obj) out.push_back({kv.k, "=", {kv.v.s}});
+      for (auto& kv : ml->obj()) out.push_back({kv.k.str(), "=", {std::string(kv.v.s())}});
   if (const Value* me = sel.get("matchExpressions"))
     if (me->is_arr())
-      for (auto& e : me->arr) {
+      for (auto& e : me->arr()) {
         std::string op = e.str_or("operator");
         LReq r{e.str_or("key"), op == "In" ? "in" : op == "NotIn" ? "notin" : op == "Exists" ? "exists" : "!", {}};
         if (const Value* vs = e.get("values"))
           if (vs->is_arr())
-            for (auto& v : vs->arr) r.vals.push_back(v.s);
+            for (auto& v : vs->arr()) r.vals.push_back(std::string(v.s()));
         out.push_back(r);
       }
   return out;
@@ -1729,11 +1855,11 @@ bool rule_match(const Value& rules, const Res& r, const std::string& op) {
   if (!rules.is_arr()) return false;
   auto has = [](const Value* list, const std::string& x) {
     if (!list || !list->is_arr()) return false;
-    for (auto& v : list->arr)
-      if (v.is_str() && (v.s == "*" || v.s == x)) return true;
+    for (auto& v : list->arr())
+      if (v.is_str() && (v.s() == "*" || v.s() == x)) return true;
     return false;
   };
-  for (auto& rule : rules.arr) {
+  for (auto& rule : rules.arr()) {
     if (!has(rule.get("operations"), op)) continue;
     if (!has(rule.get("apiGroups"), r.group)) continue;
     if (!has(rule.get("resources"), r.plural)) continue;
@@ -1777,7 +1903,7 @@ std::vector<Webhook> build_webhooks(const Res& r, const std::string& op, Bucket&
   for (auto& c : cfgs) {
     const Value* whs = c->get("webhooks");
     if (!whs || !whs->is_arr()) continue;
-    for (auto& wh : whs->arr) {
+    for (auto& wh : whs->arr()) {
       const Value* rules = wh.get("rules");
       if (!rules || !rule_match(*rules, r, op)) continue;
       Webhook w;
@@ -1786,18 +1912,18 @@ std::vector<Webhook> build_webhooks(const Res& r, const std::string& op, Bucket&
       const Value* ts = wh.get("timeoutSeconds");
       if (ts && ts->t == T::Int) w.timeout_s = (double)ts->i;
       if (const Value* ns = wh.get("namespaceSelector"))
-        if (ns->is_obj() && !ns->obj.empty()) {
+        if (ns->is_obj() && !ns->obj().empty()) {
           w.has_ns_sel = true;
           w.ns_sel = selector_reqs(*ns);
         }
       if (const Value* os = wh.get("objectSelector"))
-        if (os->is_obj() && !os->obj.empty()) {
+        if (os->is_obj() && !os->obj().empty()) {
           w.has_obj_sel = true;
           w.obj_sel = selector_reqs(*os);
         }
       if (const Value* mc = wh.get("matchConditions"))
         if (mc->is_arr())
-          for (auto& c : mc->arr) {
+          for (auto& c : mc->arr()) {
             Webhook::Cond cond;
             try {
               cond.node = std::make_shared<const CelNode>(CelParser(c.str_or("expression")).parse());
@@ -1886,19 +2012,19 @@ bool resolve_service(const Webhook& w, std::string* host, int* port) {
   std::vector<std::pair<std::string, int>> targets;
   const Value* subsets = o->get("subsets");
   if (!subsets || !subsets->is_arr()) return false;
-  for (auto& ss : subsets->arr) {
+  for (auto& ss : subsets->arr()) {
     const Value* addrs = ss.get("addresses");
     const Value* ports = ss.get("ports");
-    if (!addrs || !addrs->is_arr() || !ports || !ports->is_arr() || ports->arr.empty()) continue;
+    if (!addrs || !addrs->is_arr() || !ports || !ports->is_arr() || ports->arr().empty()) continue;
     int p = 0;
-    for (auto& pp : ports->arr) {
+    for (auto& pp : ports->arr()) {
       const Value* pv = pp.get("port");
       if (pv && pv->t == T::Int) {
         p = (int)pv->i;
         break;
       }
     }
-    for (auto& a : addrs->arr) targets.push_back({a.str_or("ip"), p});
+    for (auto& a : addrs->arr()) targets.push_back({a.str_or("ip"), p});
   }
   if (targets.empty()) return false;
   auto& t = targets[g_rr++ % targets.size()];
@@ -2274,7 +2400,7 @@ Obj do_get(const Res& r, const std::string& ns, const std::string& name) {
   return it->second;
 }
 
-void remove_locked(const Res& r, Obj live, Obj final);
+void remove_locked(const Res& r, Obj live, Obj final, int64_t rv);
 void gc_dependents(const std::string& owner_uid);
 void sync_delete_locked(const Res& r, const std::string& ns, const std::string& name);
 
@@ -2299,7 +2425,7 @@ Obj do_create(const Res& r, const std::string& url_ns, Value obj, bool dry) {
   }
   obj["apiVersion"] = Value::str(r.api_version(r.storage));
   obj = admit("CREATE", r, std::move(obj), nullptr);
-  if (auto err = validate(r, obj)) throw Invalid(r.group.empty() ? r.singular : r.kind + "." + r.group, mget(obj, "name"), *err);
+  if (auto err = validate(r, obj, nullptr)) throw Invalid(r.group.empty() ? r.singular : r.kind + "." + r.group, mget(obj, "name"), *err);
   {
     Value& mm = mdm(obj);
     mm["uid"] = Value::str(uuid4());
@@ -2316,7 +2442,8 @@ Obj do_create(const Res& r, const std::string& url_ns, Value obj, bool dry) {
   if (b.objs.count(k)) throw AlreadyExists(r.err_res(), k.second);
   defaults(r, obj, false);
   if (dry) return std::make_shared<const Value>(std::move(obj));
-  mdm(obj)["resourceVersion"] = Value::str(std::to_string(++S.rv));
+  const int64_t rv = ++S.rv;
+  mdm(obj)["resourceVersion"] = Value::str(std::to_string(rv));
   auto sp = std::make_shared<const Value>(std::move(obj));
   b.objs[k] = sp;
   {
@@ -2327,14 +2454,14 @@ Obj do_create(const Res& r, const std::string& url_ns, Value obj, bool dry) {
   }
   index_owner(r, *sp, false);
   S.writes++;
-  emit(r, "ADDED", sp, nullptr);
+  emit(r, "ADDED", sp, nullptr, rv);
   // the GC's "absent owner" rule: a dependent created after all of its owners are gone
   // (a controller acting on a stale cache) is collected right away
   if (S.gc) {
     const Value* refs = md(*sp)->get("ownerReferences");
-    if (refs && refs->is_arr() && !refs->arr.empty()) {
+    if (refs && refs->is_arr() && !refs->arr().empty()) {
       bool live = false;
-      for (auto& ref : refs->arr) {
+      for (auto& ref : refs->arr()) {
         std::string av = ref.str_or("apiVersion");
         auto slash = av.find('/');
         Res* owner = by_kind(slash == std::string::npos ? "" : av.substr(0, slash), ref.str_or("kind"));
@@ -2355,25 +2482,36 @@ Obj do_create(const Res& r, const std::string& url_ns, Value obj, bool dry) {
 
 // nw's server-owned metadata from `base` (the version it replaces); generation bumped
 // when the spec changes; no new finalizers once deletion has started
+// Members that already hold base's value (a patched copy of the stored version holds the very
+// same payloads) are left alone, so metadata that does not change is not copied either.
 void prepare_update(const Res& r, const Value& base, Value& nw) {
   Value& m = mdm(nw);
   const Value& lm = *md(base);
-  std::string ns = mget(base, "namespace"), name = mget(base, "name");
+  auto put = [&nw](const char* k, const Value& v) {
+    Value& mm = mdm(nw);  // looked up each time: defaulting below may add members to nw
+    const Value* have = mm.get(k);
+    if (!have || !have->same(v)) mm[k] = v;
+  };
+  auto put_str = [&](const char* k) {  // base's string member, "" when it has none
+    const Value* v = lm.get(k);
+    if (v && v->is_str()) put(k, *v);
+    else put(k, Value::str(""));
+  };
   for (const char* k : {"uid", "creationTimestamp", "deletionTimestamp", "deletionGracePeriodSeconds"}) {
     const Value* v = lm.get(k);
-    if (v) m[k] = *v;
+    if (v) put(k, *v);
     else m.erase(k);
   }
-  if (r.namespaced) m["namespace"] = Value::str(ns);
+  if (r.namespaced) put_str("namespace");
   else m.erase("namespace");
-  m["name"] = Value::str(name);
+  put_str("name");
   if (lm.get("deletionTimestamp")) {
     std::set<std::string> before, added;
     if (const Value* f = lm.get("finalizers"))
-      for (auto& x : f->arr) before.insert(x.s);
+      for (auto& x : f->arr()) before.insert(std::string(x.s()));
     if (const Value* f = m.get("finalizers"))
-      for (auto& x : f->arr)
-        if (!before.count(x.s)) added.insert(x.s);
+      for (auto& x : f->arr())
+        if (!before.count(std::string(x.s()))) added.insert(std::string(x.s()));
     if (!added.empty()) {
       std::string l;
       for (auto& a : added) l += (l.empty() ? "" : " ") + a;
@@ -2381,23 +2519,27 @@ void prepare_update(const Res& r, const Value& base, Value& nw) {
     }
   }
   if (S.defaulting && defaulted_kind(r)) {
-    api_defaults(r, nw);
+    // api_defaults reads and writes the spec alone, and every stored version has been through
+    // it: a spec still on the stored payload (a status or metadata write) is defaulted already
+    const Value* nspec = nw.get("spec");
+    const Value* bspec = base.get("spec");
+    if (!(nspec && bspec && nspec->same(*bspec))) api_defaults(r, nw);
     if (r.key == "services") {  // the allocated ClusterIP is immutable
       const Value* bs = base.get("spec");
       Value& ns_ = obj_at(nw, "spec");
       for (const char* k : {"clusterIP", "clusterIPs"}) {
         const Value* have = ns_.get(k);
         const Value* was = bs ? bs->get(k) : nullptr;
-        if (was && (!have || have->is_null() || (have->is_str() && have->s.empty()))) ns_[k] = *was;
+        if (was && (!have || have->is_null() || (have->is_str() && have->s().empty()))) ns_[k] = *was;
       }
     }
   }
   if (const Value* gen = lm.get("generation")) {
-    int64_t gv = gen->i;
+    int64_t gv = gen->int_or(0);
     if (!spec_equal(nw, base)) gv++;
-    m["generation"] = Value::integer(gv);
+    put("generation", Value::integer(gv));
   }
-  m["resourceVersion"] = Value::str(mget(base, "resourceVersion"));
+  put_str("resourceVersion");
 }
 
 // Commit a new version over `cur` (caller holds no lock).  The update is prepared and
@@ -2419,27 +2561,31 @@ Obj commit_update(const Res& r, const Obj& cur, Value nw) {
   auto it = b.objs.find({ns, name});
   if (it == b.objs.end()) throw NotFound(r.err_res(), name);
   Obj live = it->second;
-  if (!want_rv.empty() && want_rv != mget(*live, "resourceVersion")) throw Conflict(r.err_res(), name);
+  if (!want_rv.empty() && want_rv != mview(*live, "resourceVersion")) throw Conflict(r.err_res(), name);
   if (live != cur) {  // written since the snapshot: prepare against the live version
     prepare_update(r, *live, nw);
     noop = equal_except_meta(nw, *live);
   }
   if (noop) return live;  // no-op write
   const Value* fin = md(nw)->get("finalizers");
-  bool no_fin = !fin || !fin->is_arr() || fin->arr.empty();
+  bool no_fin = !fin || !fin->is_arr() || fin->arr().empty();
+  const int64_t rv = ++S.rv;
+  mdm(nw)["resourceVersion"] = Value::str(std::to_string(rv));
   if (md(*live)->get("deletionTimestamp") && no_fin) {
-    mdm(nw)["resourceVersion"] = Value::str(std::to_string(++S.rv));
     auto out = std::make_shared<const Value>(std::move(nw));
-    remove_locked(r, live, out);
+    remove_locked(r, live, out, rv);
     return out;
   }
-  mdm(nw)["resourceVersion"] = Value::str(std::to_string(++S.rv));
-  index_owner(r, *live, true);
+  // the owner index follows ownerReferences: untouched when the new version shares them
+  const Value* orl = md(*live)->get("ownerReferences");
+  const Value* orn = md(nw)->get("ownerReferences");
+  const bool owners_same = orl ? (orn && orl->same(*orn)) : !orn;
+  if (!owners_same) index_owner(r, *live, true);
   auto sp = std::make_shared<const Value>(std::move(nw));
   it->second = sp;
-  index_owner(r, *sp, false);
+  if (!owners_same) index_owner(r, *sp, false);
   S.writes++;
-  emit(r, "MODIFIED", sp, live);
+  emit(r, "MODIFIED", sp, live, rv);
   return sp;
 }
 
@@ -2453,19 +2599,19 @@ Obj do_update(const Res& r, const std::string& ns, const std::string& name, Valu
   }
   nw["apiVersion"] = Value::str(r.api_version(r.storage));
   if (sub == "status") {
-    Value merged = *cur;
+    Value merged = *cur;  // shares everything; the root's members are copied once, below
     if (const Value* st = nw.get("status")) merged["status"] = *st;
     else merged.erase("status");
     mdm(merged)["resourceVersion"] = Value::str(mget(nw, "resourceVersion"));
     nw = std::move(merged);
-    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    if (auto err = validate(r, nw, cur.get())) throw Invalid(r.kind + "." + r.group, name, *err);
   } else {
     if (r.status) {
       if (const Value* st = cur->get("status")) nw["status"] = *st;
       else nw.erase("status");
     }
     nw = admit("UPDATE", r, std::move(nw), cur.get());
-    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    if (auto err = validate(r, nw, cur.get())) throw Invalid(r.kind + "." + r.group, name, *err);
   }
   return commit_update(r, cur, std::move(nw));
 }
@@ -2483,9 +2629,9 @@ Obj do_patch_once(const Res& r, const std::string& ns, const std::string& name, 
   bool precond = pm && pm->is_obj() && !pm->str_or("resourceVersion").empty();
   if (sub == "status" && ptype == "merge" && patch.is_obj()) {
     // The status subresource takes the patched status (and a resourceVersion precondition)
-    // and nothing else, so a merge patch is applied to that member of ONE copy of the stored
-    // object; the general path below patches a copy whole and then copies the stored object
-    // a second time to put the status into.
+    // and nothing else, so a merge patch is applied to that member alone: the new version
+    // copies the root's members and the path to what the patch changes, and shares the rest
+    // (spec, metadata, the untouched parts of the status) with the stored one.
     Value nw;
     {
       PhaseTimer pt(PH_PATCH);
@@ -2498,7 +2644,7 @@ Obj do_patch_once(const Res& r, const std::string& ns, const std::string& name, 
       }
       if (precond) mdm(nw)["resourceVersion"] = Value::str(pm->str_or("resourceVersion"));
     }
-    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    if (auto err = validate(r, nw, cur.get())) throw Invalid(r.kind + "." + r.group, name, *err);
     return commit_update(r, cur, std::move(nw));
   }
   Value nw;
@@ -2511,21 +2657,26 @@ Obj do_patch_once(const Res& r, const std::string& ns, const std::string& name, 
   } catch (const PatchErr& e) {
     throw Invalid(r.kind, name, e.msg);
   }
-  if (!precond) mdm(nw)["resourceVersion"] = Value::str(mget(*cur, "resourceVersion"));
+  if (!precond) {
+    const Value* have = md(nw) ? md(nw)->get("resourceVersion") : nullptr;
+    const Value* was = md(*cur)->get("resourceVersion");
+    if (!(have && was && was->is_str() && have->same(*was))) mdm(nw)["resourceVersion"] = Value::str(mget(*cur, "resourceVersion"));
+  }
   if (sub == "status") {
+    // the patched status goes into the stored version: only the root's members are copied
     Value merged = *cur;
     const Value* st = nw.get("status");
     merged["status"] = st ? *st : Value();
     mdm(merged)["resourceVersion"] = Value::str(mget(nw, "resourceVersion"));
     nw = std::move(merged);
-    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    if (auto err = validate(r, nw, cur.get())) throw Invalid(r.kind + "." + r.group, name, *err);
   } else {
     if (r.status) {
       if (const Value* st = cur->get("status")) nw["status"] = *st;
       else nw.erase("status");
     }
     nw = admit("UPDATE", r, std::move(nw), cur.get());
-    if (auto err = validate(r, nw)) throw Invalid(r.kind + "." + r.group, name, *err);
+    if (auto err = validate(r, nw, cur.get())) throw Invalid(r.kind + "." + r.group, name, *err);
   }
   return commit_update(r, cur, std::move(nw));
 }
@@ -2546,7 +2697,7 @@ Obj do_patch(const Res& r, const std::string& ns, const std::string& name, const
   }
 }
 
-void remove_locked(const Res& r, Obj live, Obj fp) {
+void remove_locked(const Res& r, Obj live, Obj fp, int64_t rv) {
   std::string ns = mget(*live, "namespace"), name = mget(*live, "name"), uid = mget(*live, "uid");
   bucket(r).objs.erase({ns, name});
   {
@@ -2556,14 +2707,14 @@ void remove_locked(const Res& r, Obj live, Obj fp) {
   }
   index_owner(r, *live, true);
   S.writes++;
-  emit(r, "DELETED", fp, live);
+  emit(r, "DELETED", fp, live, rv);
   if (S.gc) t_gc.push_back(uid);  // cascaded once the lock is released (run_gc)
   // foreground owners waiting for their last dependent: re-checked after the commit, each
   // under its own resource's lock (fg_recheck)
   if (S.gc) {
     const Value* refs = md(*fp) ? md(*fp)->get("ownerReferences") : nullptr;
     if (refs && refs->is_arr())
-      for (auto& ref : refs->arr) {
+      for (auto& ref : refs->arr()) {
         std::string u = ref.str_or("uid");
         if (!u.empty()) t_fg.push_back(u);
       }
@@ -2595,22 +2746,23 @@ void fg_recheck(const std::string& u) {
   const Value* f = md(*it->second)->get("finalizers");
   bool fg = false;
   if (f && f->is_arr())
-    for (auto& x : f->arr)
-      if (x.s == "foregroundDeletion") fg = true;
+    for (auto& x : f->arr())
+      if (x.s() == "foregroundDeletion") fg = true;
   if (!fg) return;
   Value nw = *it->second;
   Value nf = Value::array();
-  for (auto& x : f->arr)
-    if (x.s != "foregroundDeletion") nf.arr.push_back(x);
+  for (auto& x : f->arr())
+    if (x.s() != "foregroundDeletion") nf.arr_mut().push_back(x);
   mdm(nw)["finalizers"] = nf;
-  mdm(nw)["resourceVersion"] = Value::str(std::to_string(++S.rv));
+  const int64_t rv = ++S.rv;
+  mdm(nw)["resourceVersion"] = Value::str(std::to_string(rv));
   Obj old = it->second;
-  if (nf.arr.empty()) {
-    remove_locked(*orr, old, std::make_shared<const Value>(std::move(nw)));
+  if (nf.arr().empty()) {
+    remove_locked(*orr, old, std::make_shared<const Value>(std::move(nw)), rv);
   } else {
     auto sp = std::make_shared<const Value>(std::move(nw));
     it->second = sp;
-    emit(*orr, "MODIFIED", sp, old);
+    emit(*orr, "MODIFIED", sp, old, rv);
   }
 }
 
@@ -2619,19 +2771,21 @@ void sync_delete_locked(const Res& r, const std::string& ns, const std::string& 
   if (it == bucket(r).objs.end()) return;
   Obj cur = it->second;
   const Value* f = md(*cur)->get("finalizers");
-  if (f && f->is_arr() && !f->arr.empty()) {
+  if (f && f->is_arr() && !f->arr().empty()) {
     if (md(*cur)->get("deletionTimestamp")) return;
     Value nw = *cur;
     mdm(nw)["deletionTimestamp"] = Value::str(rfc3339_now());
-    mdm(nw)["resourceVersion"] = Value::str(std::to_string(++S.rv));
+    const int64_t rv = ++S.rv;
+    mdm(nw)["resourceVersion"] = Value::str(std::to_string(rv));
     auto sp = std::make_shared<const Value>(std::move(nw));
     it->second = sp;
-    emit(r, "MODIFIED", sp, cur);
+    emit(r, "MODIFIED", sp, cur, rv);
     return;
   }
   Value final = *cur;
-  mdm(final)["resourceVersion"] = Value::str(std::to_string(++S.rv));
-  remove_locked(r, cur, std::make_shared<const Value>(std::move(final)));
+  const int64_t rv = ++S.rv;
+  mdm(final)["resourceVersion"] = Value::str(std::to_string(rv));
+  remove_locked(r, cur, std::make_shared<const Value>(std::move(final)), rv);
 }
 
 // Background cascade for a removed (or foreground-deleting) owner: each dependent whose
@@ -2654,7 +2808,7 @@ void gc_dependents(const std::string& owner_uid) {
     if (oit == b.objs.end()) continue;
     bool other_live = false;
     if (const Value* refs = md(*oit->second)->get("ownerReferences")) {
-      for (auto& ref : refs->arr) {
+      for (auto& ref : refs->arr()) {
         std::string u = ref.str_or("uid");
         if (u == owner_uid) continue;
         IdxStripe& st = idx(u);
@@ -2707,32 +2861,34 @@ Value do_delete(const Res& r, const std::string& ns_, const std::string& name, c
     if (f->is_arr()) fins = *f;
   std::string prop = opts.str_or("propagationPolicy", "Background");
   bool has_fg = false;
-  for (auto& x : fins.arr)
-    if (x.s == "foregroundDeletion") has_fg = true;
-  if (prop == "Foreground" && S.gc && !has_fg) fins.arr.push_back(Value::str("foregroundDeletion"));
-  if (!fins.arr.empty()) {
+  for (auto& x : fins.arr())
+    if (x.s() == "foregroundDeletion") has_fg = true;
+  if (prop == "Foreground" && S.gc && !has_fg) fins.arr_mut().push_back(Value::str("foregroundDeletion"));
+  if (!fins.arr().empty()) {
     if (md(*cur)->get("deletionTimestamp")) return *cur;
     Value nw = *cur;
     Value& m = mdm(nw);
     m["finalizers"] = fins;
     m["deletionTimestamp"] = Value::str(rfc3339_now());
     m["deletionGracePeriodSeconds"] = Value::integer(0);
-    if (Value* gen = m.get("generation")) gen->i += 1;
-    m["resourceVersion"] = Value::str(std::to_string(++S.rv));
+    if (Value* gen = m.get_mut("generation"); gen && gen->t == T::Int) gen->i += 1;
+    const int64_t rv = ++S.rv;
+    m["resourceVersion"] = Value::str(std::to_string(rv));
     auto sp = std::make_shared<const Value>(std::move(nw));
     it->second = sp;
     S.writes++;
-    emit(r, "MODIFIED", sp, cur);
+    emit(r, "MODIFIED", sp, cur, rv);
     bool fg = false;
-    for (auto& x : fins.arr)
-      if (x.s == "foregroundDeletion") fg = true;
+    for (auto& x : fins.arr())
+      if (x.s() == "foregroundDeletion") fg = true;
     if (fg) t_gc.push_back(mget(*cur, "uid"));  // dependents first, after this commit (run_gc)
     return *sp;
   }
   Value final = *cur;
-  mdm(final)["resourceVersion"] = Value::str(std::to_string(++S.rv));
+  const int64_t rv = ++S.rv;
+  mdm(final)["resourceVersion"] = Value::str(std::to_string(rv));
   Value out = final;
-  remove_locked(r, cur, std::make_shared<const Value>(std::move(final)));
+  remove_locked(r, cur, std::make_shared<const Value>(std::move(final)), rv);
   return out;
 }
 
@@ -2799,24 +2955,24 @@ thread_local AuditCtx t_aud;
 
 bool audit_list_has(const Value* v, const std::string& x) {
   if (!v || !v->is_arr()) return true;  // unset: matches everything
-  for (auto& e : v->arr)
-    if (e.s == x) return true;
+  for (auto& e : v->arr())
+    if (e.s() == x) return true;
   return false;
 }
 
 std::string audit_level(const std::string& user, const std::string& verb, const std::string& ns,
                         const std::string& group, const std::string& resource, const std::string& sub) {
-  for (auto& r : g_audit.rules.arr) {
-    if (const Value* u = r.get("users"); u && u->is_arr() && !u->arr.empty() && !audit_list_has(u, user)) continue;
-    if (const Value* v = r.get("verbs"); v && v->is_arr() && !v->arr.empty() && !audit_list_has(v, verb)) continue;
+  for (auto& r : g_audit.rules.arr()) {
+    if (const Value* u = r.get("users"); u && u->is_arr() && !u->arr().empty() && !audit_list_has(u, user)) continue;
+    if (const Value* v = r.get("verbs"); v && v->is_arr() && !v->arr().empty() && !audit_list_has(v, verb)) continue;
     if (const Value* n = r.get("namespaces"); n && n->is_arr() && !audit_list_has(n, ns)) continue;
-    if (const Value* rs = r.get("resources"); rs && rs->is_arr() && !rs->arr.empty()) {
+    if (const Value* rs = r.get("resources"); rs && rs->is_arr() && !rs->arr().empty()) {
       bool hit = false;
       std::string full = sub.empty() ? resource : resource + "/" + sub;
-      for (auto& gr : rs->arr) {
+      for (auto& gr : rs->arr()) {
         if (gr.str_or("group") != group) continue;
         const Value* names = gr.get("resources");
-        if (!names || !names->is_arr() || names->arr.empty() || audit_list_has(names, resource) ||
+        if (!names || !names->is_arr() || names->arr().empty() || audit_list_has(names, resource) ||
             audit_list_has(names, full)) {
           hit = true;
           break;
@@ -2856,12 +3012,12 @@ void audit_write(const AuditCtx& a, const std::string& uri, const std::string& u
   Value user = Value::object();
   user["username"] = Value::str("system:admin");
   Value groups = Value::array();
-  groups.arr.push_back(Value::str("system:masters"));
-  groups.arr.push_back(Value::str("system:authenticated"));
+  groups.arr_mut().push_back(Value::str("system:masters"));
+  groups.arr_mut().push_back(Value::str("system:authenticated"));
   user["groups"] = std::move(groups);
   ev["user"] = std::move(user);
   Value ips = Value::array();
-  ips.arr.push_back(Value::str("127.0.0.1"));
+  ips.arr_mut().push_back(Value::str("127.0.0.1"));
   ev["sourceIPs"] = std::move(ips);
   ev["userAgent"] = Value::str(ua);
   Value ref = Value::object();
@@ -3179,7 +3335,7 @@ Value discovery(const std::string& p, bool* found) {
     Value v = Value::object();
     v["kind"] = Value::str("APIVersions");
     Value vs = Value::array();
-    vs.arr.push_back(Value::str("v1"));
+    vs.arr_mut().push_back(Value::str("v1"));
     v["versions"] = vs;
     return v;
   }
@@ -3203,11 +3359,11 @@ Value discovery(const std::string& p, bool* found) {
         Value x = Value::object();
         x["groupVersion"] = Value::str(kv.first + "/" + ver);
         x["version"] = Value::str(ver);
-        vers.arr.push_back(x);
+        vers.arr_mut().push_back(x);
       }
       g["versions"] = vers;
-      g["preferredVersion"] = vers.arr[0];
-      gl.arr.push_back(g);
+      g["preferredVersion"] = vers.arr()[0];
+      gl.arr_mut().push_back(g);
     }
     v["groups"] = gl;
     return v;
@@ -3235,19 +3391,19 @@ Value discovery(const std::string& p, bool* found) {
     e["namespaced"] = Value::boolean(r->namespaced);
     e["kind"] = Value::str(r->kind);
     Value verbs = Value::array();
-    for (const char* vb : {"create", "delete", "get", "list", "patch", "update", "watch"}) verbs.arr.push_back(Value::str(vb));
+    for (const char* vb : {"create", "delete", "get", "list", "patch", "update", "watch"}) verbs.arr_mut().push_back(Value::str(vb));
     e["verbs"] = verbs;
-    list.arr.push_back(e);
+    list.arr_mut().push_back(e);
     if (r->status) {
       Value st = Value::object();
       st["name"] = Value::str(r->plural + "/status");
       st["singularName"] = Value::str("");
       st["namespaced"] = Value::boolean(r->namespaced);
       st["kind"] = Value::str(r->kind);
-      list.arr.push_back(st);
+      list.arr_mut().push_back(st);
     }
   }
-  if (list.arr.empty()) {
+  if (list.arr().empty()) {
     *found = false;
     return Value();
   }
@@ -3908,7 +4064,7 @@ void load_config(const std::string& path) {
   Value cfg = kj::parse(ss.str());
   const Value* res = cfg.get("resources");
   if (!res || !res->is_arr()) throw std::runtime_error("config: resources[] required");
-  for (auto& r : res->arr) {
+  for (auto& r : res->arr()) {
     auto x = std::make_unique<Res>();
     x->group = r.str_or("group");
     x->kind = r.str_or("kind");
@@ -3918,16 +4074,16 @@ void load_config(const std::string& path) {
     x->storage = r.str_or("storageVersion");
     x->key = x->group.empty() ? x->plural : x->plural + "." + x->group;
     if (const Value* v = r.get("versions"))
-      for (auto& s : v->arr) x->versions.push_back(s.s);
-    if (const Value* v = r.get("namespaced")) x->namespaced = v->b;
-    if (const Value* v = r.get("status")) x->status = v->b;
-    if (const Value* v = r.get("installed")) x->installed = v->b;
+      for (auto& s : v->arr()) x->versions.push_back(std::string(s.s()));
+    if (const Value* v = r.get("namespaced")) x->namespaced = v->t == T::Bool && v->b;
+    if (const Value* v = r.get("status")) x->status = v->t == T::Bool && v->b;
+    if (const Value* v = r.get("installed")) x->installed = v->t == T::Bool && v->b;
     g_res.push_back(std::move(x));
   }
-  if (const Value* v = cfg.get("gc")) S.gc = v->b;
-  if (const Value* v = cfg.get("defaulting")) S.defaulting = v->b;
+  if (const Value* v = cfg.get("gc")) S.gc = v->t == T::Bool && v->b;
+  if (const Value* v = cfg.get("defaulting")) S.defaulting = v->t == T::Bool && v->b;
   if (const Value* v = cfg.get("schemas"); v && v->is_obj())
-    for (auto& m : v->obj) g_schemas[m.k] = m.v;
+    for (auto& m : v->obj()) g_schemas[m.k.str()] = m.v;
   if (const Value* v = cfg.get("history"))
     if (v->t == T::Int) S.history = (size_t)v->i;
   g_token = cfg.str_or("token");
@@ -3936,7 +4092,7 @@ void load_config(const std::string& path) {
     if (const Value* pol = a->get("policy"); pol && pol->is_obj()) {
       if (const Value* rules = pol->get("rules"); rules && rules->is_arr()) g_audit.rules = *rules;
       if (const Value* om = pol->get("omitStages"); om && om->is_arr())
-        for (auto& x : om->arr) g_audit.omit.insert(x.s);
+        for (auto& x : om->arr()) g_audit.omit.insert(std::string(x.s()));
     }
     g_audit.on = !g_audit.path.empty();
   }
