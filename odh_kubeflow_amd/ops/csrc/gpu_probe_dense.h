@@ -19,7 +19,10 @@
 // 2s + (lane >> 5) of its row.  Neither path has scale operands and the k order inside an
 // instruction is the same for A and B, so it cannot change a dot product: no operand map has to
 // be fitted (tests/test_gpu_dense_exact.py holds the kernels to a host product on random,
-// asymmetric integer data all the same).  C/D is the 32x32 map of the bf16 kernels.
+// asymmetric integer data all the same; tests/test_gpu_lowprec_sweeps.py multiplies 256 half
+// values by each other and holds the fused check to the exact mismatch count and per-XCD
+// attribution of a changed element in every row and every column, and of a NaN and an inf).
+// C/D is the 32x32 map of the bf16 kernels.
 //
 // Tile and pipeline: those of gemm256d_kernel — 512 threads, 8 waves as 2×4, 128×64 outputs per
 // wave, the 4-buffer LDS-DMA ring with three stages in flight across counted-vmcnt raw

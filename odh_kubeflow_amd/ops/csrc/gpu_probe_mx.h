@@ -20,6 +20,12 @@
 //     either block, and the hardware scales its upper four VGPRs by the scale in lane (l & 31) + 32.
 // C/D is the 32x32 map of the bf16 kernels.
 //
+// Tests: tests/test_gpu_mx_exact.py (random codes and scales against tests/mx_reference.py) and
+// tests/test_gpu_lowprec_sweeps.py: every FP8 code against every FP8 code (the subnormals and
+// both NaN codes decode as OCP e4m3fn says), every FP4 code pair, every E8M0 byte 1 … 254, and
+// the fused check's exact mismatch count and per-XCD attribution for a changed element and a
+// changed scale byte in every row and every column.
+//
 // Tile: the 256×256 tile of gemm256_kernel (512 threads, 8 waves as 2×4, 128×64 outputs per
 // wave), 16 KiB per operand stage = 256 rows × 64 bytes (BK = 64 FP8 or 128 FP4 elements),
 // staged by global_load_lds of 16 B with the XOR swizzle of the deep bf16 kernel on the source

@@ -93,3 +93,73 @@ def zero_classes(k):
     if k <= 0 or k % 128:
         return -1
     return int((probe_table(k) == 0).sum())
+
+
+# ------------------------------------------------------------------ one-hot cases of the store kernel
+#
+# Each row of A holds one non-zero code and Bt one code throughout, so every output is a single
+# product (plus exact zeros): exact whatever order or width the hardware sums in.  The expected
+# values come from the formats' definitions, element by element; ``product`` (the matrix
+# product of the decoded, scaled operands) must agree, which ``test_probe_mx.py`` checks.
+
+ALL_CODES_M = ALL_CODES_N = 256
+SCALE_LO, SCALE_HI = 119, 135  # seeded scales of the one-hot cases: 2^-8 .. 2^8
+
+
+def all_codes_case(fmt):
+    """Every code of ``fmt`` against every code, 256 × 256 at one stage (K = 64 FP8, 128 FP4).
+
+    FP8: ``A[i][k]`` is code ``i`` at ``k = i % 64`` and ``0x00`` elsewhere, ``Bt[j][k]`` is code
+    ``j`` at every k.  FP4: nibble code ``i % 16`` (-0, code 8, included) at ``k = i % 128``, and
+    ``Bt[j]`` is nibble ``j % 16`` throughout.  Scales are seeded per row and block in 119 .. 135.
+    Returns ``a, bt, sa, sbt, want`` with ``want[i][j] = decode(i) · decode(j) · 2^(sA + sBt - 254)``
+    of the block that holds row i's element; rows and columns of the FP8 codes 0x7f and 0xff
+    are NaN."""
+    m, n = ALL_CODES_M, ALL_CODES_N
+    i, j = np.arange(m), np.arange(n)
+    rng = np.random.default_rng(20240 + fmt)
+    if fmt == FP8:
+        k = 64
+        hot = i % k
+        a = np.zeros((m, k), dtype=np.uint8)
+        a[i, hot] = i
+        bt = np.repeat(j.astype(np.uint8)[:, None], k, axis=1)
+        da, db = decode_fp8(i), decode_fp8(j)
+    else:
+        k = 128
+        hot = i % k
+        a = np.zeros((m, k // 2), dtype=np.uint8)
+        a[i, hot // 2] = (i % 16) << (4 * (hot & 1))
+        bt = np.repeat(((j % 16) * 0x11).astype(np.uint8)[:, None], k // 2, axis=1)
+        sign = np.where(np.arange(16) & 8, -1.0, 1.0)
+        da, db = (sign * FP4_VALUES[np.arange(16) & 7])[i % 16], (sign * FP4_VALUES[np.arange(16) & 7])[j % 16]
+    sa = rng.integers(SCALE_LO, SCALE_HI + 1, size=(m, k // 32), dtype=np.uint8)
+    sbt = rng.integers(SCALE_LO, SCALE_HI + 1, size=(n, k // 32), dtype=np.uint8)
+    blk = hot // 32
+    e = sa[i, blk].astype(np.int64)[:, None] + sbt[:, blk].astype(np.int64).T - 254  # [i][j]
+    want = da[:, None] * db[None, :] * 2.0 ** e.astype(np.float64)
+    return a, bt, sa, sbt, want
+
+
+E8M0_K = 8192  # 256 blocks: row i's one element sits in block i
+
+
+def e8m0_range_case():
+    """FP8, every scale byte 1 .. 254 on the A side: ``A[i][32 i]`` is 1.0 (code 0x38), the rest of
+    the row 0x00, and Bt is 1.0 throughout.  The scale of block b is ``min(max(b, 1), 254)`` in
+    every row of A, so row i's element is scaled by byte i (rows 0 and 255 reuse 1 and 254);
+    ``sBt[j][b]`` is ``254 - sA[b] + ((j mod 41) - 20)`` kept inside 1 .. 254.  The two exponents
+    of a block then sum to -20 .. 20 in *every* block, also where A is zero, so no partial
+    product leaves fp32's range however the hardware forms it.  ``want[i][j]`` is the power of
+    two ``2^(sA[i][i] + sBt[j][i] - 254)``."""
+    m, n, k = ALL_CODES_M, ALL_CODES_N, E8M0_K
+    i, j, b = np.arange(m), np.arange(n), np.arange(k // 32)
+    a = np.zeros((m, k), dtype=np.uint8)
+    a[i, 32 * i] = 0x38
+    bt = np.full((n, k), 0x38, dtype=np.uint8)
+    sblock = np.clip(b, 1, 254)
+    sa = np.repeat(sblock[None, :], m, axis=0).astype(np.uint8)
+    sbt = np.clip(254 - sblock[None, :] + (j[:, None] % 41 - 20), 1, 254).astype(np.uint8)
+    e = sa[i, i].astype(np.int64)[:, None] + sbt[:, i].astype(np.int64).T - 254  # [i][j]
+    assert e.min() >= -20 and e.max() <= 20
+    return a, bt, sa, sbt, 2.0 ** e.astype(np.float64)

@@ -94,6 +94,35 @@ def fused_tile_id(tm, tn, tiles_m, tiles_n, gm=1):
     return tm * tiles_n + tn
 
 
+# ------------------------------------------------------------------ f16: value against value
+
+
+def f16_values():
+    """256 half bit patterns (uint16) for the one-hot f16 case: the integers -8 .. 8, ±65504, the
+    smallest normal, ±0, the all-ones mantissa of every normal exponent, and seeded random normal
+    patterns in 0x0400 .. 0x7bff for the rest.  No subnormal, inf or NaN."""
+    fixed = [np.arange(-8, 9).astype(np.float16).view(np.uint16), np.array([0x7BFF, 0xFBFF, 0x0400, 0x0000, 0x8000]),
+             (np.arange(1, 31) << 10) | 0x03FF]
+    fixed = np.concatenate([np.asarray(x, dtype=np.uint16) for x in fixed])
+    rng = np.random.default_rng(160016)
+    rest = rng.integers(0x0400, 0x7C00, size=256 - fixed.size, dtype=np.uint16)
+    return np.concatenate([fixed, rest])
+
+
+def f16_onehot_case():
+    """Every value of ``f16_values`` against every value, 256 × 256 at one stage (K = 32):
+    ``A[i][k]`` is value ``i`` at ``k = i % 32`` and +0 elsewhere, ``Bt[j][k]`` is value ``j`` at
+    every k.  Each output is one product of two halves: 22 significant bits, exact in fp32 (and
+    in the float64 computed here).  Returns ``a, bt`` (float16) and ``want`` (float64)."""
+    v = f16_values()
+    i = np.arange(256)
+    a = np.zeros((256, 32), dtype=np.uint16)
+    a[i, i % 32] = v
+    bt = np.repeat(v[:, None], 32, axis=1)
+    x = v.view(np.float16).astype(np.float64)
+    return a.view(np.float16), bt.view(np.float16), x[:, None] * x[None, :]
+
+
 # ------------------------------------------------------------------ busy kernel
 
 

@@ -112,6 +112,12 @@ def test_dense_gemm_exact_over_grids(dev, fmt, m, n):
     _exact_store(dev, fmt, m, n, _stage(fmt))
 
 
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_dense_gemm_exact_over_tiles_and_stages(dev, fmt):
+    """2 × 3 tiles at 3 stages: operand addresses with a tile offset and ``kt > 0``."""
+    _exact_store(dev, fmt, 512, 768, 3 * _stage(fmt))
+
+
 # ------------------------------------------------------------------ entry points refuse
 
 

@@ -114,6 +114,12 @@ def test_mx_gemm_exact_over_grids(dev, fmt, m, n):
     _exact_store(dev, fmt, m, n, _stage(fmt))
 
 
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_mx_gemm_exact_over_tiles_and_stages(dev, fmt):
+    """2 × 3 tiles at 3 stages: operand and scale addresses with a tile offset and ``kt > 0``."""
+    _exact_store(dev, fmt, 512, 768, 3 * _stage(fmt))
+
+
 def test_mx_entry_points_check_before_launch(dev):
     gpu = _gpu()
     a, bt, sa, sbt, _ = _random_case("fp8", 256, 256, 64)

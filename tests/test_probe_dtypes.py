@@ -186,3 +186,26 @@ def test_table_is_the_product_of_the_operands(fmt, k):
     t = dense_table(fmt, k)
     assert np.array_equal(want, t[np.arange(m)[:, None] % 5, np.arange(n)[None, :] % 7])
     assert t.any()  # K % 35 != 0: not the vacuous all-zero check
+
+
+def test_f16_onehot_case_is_exact_in_fp32():
+    v = ref.f16_values()
+    assert v.dtype == np.uint16 and v.size == 256
+    e = (v >> 10) & 31
+    assert (((e >= 1) & (e <= 30)) | ((v & 0x7FFF) == 0)).all()  # normal or ±0: no subnormal, inf, NaN
+    x = v.view(np.float16).astype(np.float64)
+    for want in (*range(-8, 9), 65504.0, -65504.0, 2.0 ** -14):
+        assert want in x
+    assert {0x0000, 0x8000} <= set(v.tolist())
+    assert all(((ee << 10) | 0x3FF) in v for ee in range(1, 31))  # all-ones mantissas
+    a, bt, want = ref.f16_onehot_case()
+    assert a.dtype == bt.dtype == np.float16 and a.shape == bt.shape == (256, 32)
+    nz = (a.view(np.uint16) != 0).sum(axis=1)
+    assert np.array_equal(nz, (v != 0).astype(np.int64))  # one non-zero code per row (none for +0)
+    assert np.array_equal(a.view(np.uint16)[np.arange(256), np.arange(256) % 32], v)
+    assert (bt.view(np.uint16) == v[:, None]).all()
+    assert np.isfinite(want).all()
+    assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
+    nzw = np.abs(want[want != 0])
+    assert nzw.min() >= 2.0 ** -28 and nzw.max() <= 65504.0 ** 2  # fp32 normals
+    assert np.array_equal(a.astype(np.float64) @ bt.astype(np.float64).T, want)

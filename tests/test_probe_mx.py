@@ -155,3 +155,66 @@ def test_table_is_the_product_of_the_operands(k):
         want = ref.product(fmt, ref.encode(fmt, va), ref.encode(fmt, vb), ref.probe_scales(m, k),
                            ref.probe_scales(n, k))
         assert np.array_equal(want, t[np.arange(m)[:, None] % ref.ROWS, np.arange(n)[None, :] % ref.COLS])
+
+
+# ------------------------------------------------------------------ the one-hot cases
+
+
+def _one_nonzero_code_per_row(codes):
+    return ((codes != 0).sum(axis=1) == 1).all()
+
+
+@pytest.mark.parametrize("fmt", [ref.FP8, ref.FP4])
+def test_all_codes_case_is_exact_in_fp32(fmt):
+    a, bt, sa, sbt, want = ref.all_codes_case(fmt)
+    k = a.shape[1] * (2 if fmt == ref.FP4 else 1)
+    assert a.shape[0] == bt.shape[0] == 256 and k == (128 if fmt == ref.FP4 else 64)
+    assert sa.shape == sbt.shape == (256, k // 32)
+    assert min(sa.min(), sbt.min()) >= 119 and max(sa.max(), sbt.max()) <= 135
+    assert len(np.unique(sa)) == len(np.unique(sbt)) == 17  # every scale 119 .. 135 occurs
+    # one non-zero byte per row of A (row 0 of FP8 and rows 0 mod 16 of FP4 hold code 0: none)
+    nz = (a != 0).sum(axis=1)
+    zero_rows = np.arange(256) % (16 if fmt == ref.FP4 else 256) == 0
+    assert np.array_equal(nz, np.where(zero_rows, 0, 1))
+    if fmt == ref.FP8:
+        assert np.array_equal(a[np.arange(256), np.arange(256) % 64], np.arange(256))
+        assert all((bt[j] == j).all() for j in range(256))
+        nan = np.isin(np.arange(256), [0x7F, 0xFF])
+    else:
+        nib = np.stack([a & 15, a >> 4], axis=-1).reshape(256, 128)
+        assert np.array_equal(nib[np.arange(256), np.arange(256) % 128], np.arange(256) % 16)
+        assert all((bt[j] == (j % 16) * 0x11).all() for j in range(256))
+        nan = np.zeros(256, dtype=bool)
+    # NaN exactly in the rows and columns of the two NaN codes; every other value survives fp32
+    assert np.array_equal(np.isnan(want), nan[:, None] | nan[None, :])
+    fin = want[~np.isnan(want)]
+    assert np.array_equal(fin.astype(np.float32).astype(np.float64), fin)
+    with np.errstate(invalid="ignore"):
+        full = ref.product(fmt, a, bt, sa, sbt)
+    assert np.array_equal(np.isnan(full), np.isnan(want)) and np.array_equal(full[~np.isnan(want)], fin)
+    # also times 2^±16, the widest scales a pair of blocks could add beyond the seeded ones
+    for s in (2.0 ** 16, 2.0 ** -16):
+        assert np.array_equal((fin * s).astype(np.float32).astype(np.float64), fin * s)
+    if fmt == ref.FP8:  # all 254² finite pairs are there, each a product of the decoded codes
+        d = ref.decode_fp8(np.arange(256))
+        assert np.isfinite(d).sum() == 254 and fin.size == 254 * 254
+        e = np.log2(np.abs(want[0x38, 0x38]))
+        assert e == int(e) and -16 <= e <= 16  # 1.0 · 1.0 · the two scales
+
+
+def test_e8m0_range_case_is_powers_of_two():
+    a, bt, sa, sbt, want = ref.e8m0_range_case()
+    assert a.shape == bt.shape == (256, ref.E8M0_K) and sa.shape == sbt.shape == (256, ref.E8M0_K // 32)
+    assert _one_nonzero_code_per_row(a) and (a[np.arange(256), 32 * np.arange(256)] == 0x38).all()
+    assert (bt == 0x38).all()
+    hot = sa[np.arange(256), np.arange(256)]
+    assert hot.tolist() == [1] + list(range(1, 255)) + [254]  # every byte 1 .. 254 scales an element
+    assert min(sa.min(), sbt.min()) >= 1 and max(sa.max(), sbt.max()) <= 254
+    # every block's pair of scales stays within 2^±20, whichever row and column meet in it
+    pair = sa[0].astype(np.int64)[None, :] + sbt.astype(np.int64) - 254
+    assert (sa == sa[0]).all() and pair.min() >= -20 and pair.max() <= 20
+    m, e = np.frexp(want)
+    assert (m == 0.5).all() and (e - 1).min() >= -20 and (e - 1).max() <= 20  # normal powers of two
+    assert len(np.unique(e)) == 41
+    assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
+    assert np.array_equal(ref.product(ref.FP8, a, bt, sa, sbt), want)
