@@ -177,16 +177,17 @@ DEFAULT_GPU_PROBE_IMAGE = "quay.io/opendatahub/odh-kubeflow-amd-gpu-probe:main" 
 GPU_PROBE_TIMEOUT_MS = "30000"
 GPU_PROBE_RCCL_MIB = "64"  # all-reduce size of the RCCL step (annotation token "rccl")
 GPU_PROBE_MX_FORMATS = "fp8,fp4"  # block-scaled formats of the MX step (annotation token "mx")
+GPU_PROBE_MX_ALL_FORMATS = "fp8,fp4,bf8,fp6,bf6"  # every format of the instruction (token "mxall")
 GPU_PROBE_DTYPES_FORMATS = "f16,i8"  # dense formats of the dtypes step (annotation token "dtypes")
 
 
-GPU_PROBE_TOKENS = ("true", "rccl", "mx", "dtypes", "false")
+GPU_PROBE_TOKENS = ("true", "rccl", "mx", "mxall", "dtypes", "false")
 
 
 def gpu_probe_tokens(nb: dict) -> frozenset:
     """The ``amd.com/gpu-probe`` annotation as a set of tokens.  It is a comma list of ``true``,
-    ``rccl``, ``mx``, ``dtypes`` and ``false``: ``rccl``, ``mx`` and ``dtypes`` each turn the probe on
-    and add their step, so ``"rccl,mx"`` runs both.  A value with an unknown token, or with
+    ``rccl``, ``mx``, ``mxall``, ``dtypes`` and ``false``: ``rccl``, ``mx``, ``mxall`` and ``dtypes`` each
+    turn the probe on and add their step, so ``"rccl,mx"`` runs both.  A value with an unknown token, or with
     ``false`` next to another token, is ignored as a whole (the empty set), like an unknown value."""
     v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
     tokens = frozenset(t.strip() for t in v.split(",")) if v else frozenset()
@@ -222,6 +223,13 @@ def gpu_probe_mx(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
     return "mx" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_MX", "false") == "true"
 
 
+def gpu_probe_mx_all(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
+    """Whether the MX step checks all five operand formats of the block-scaled instruction
+    (``--mx fp8,fp4,bf8,fp6,bf6``): ``mxall`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_MX_ALL=true`` for
+    every probed notebook.  It contains ``mx``: ``"mx,mxall"`` gives the one ``--mx`` argument."""
+    return "mxall" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_MX_ALL", "false") == "true"
+
+
 def gpu_probe_dtypes(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
     """Whether the probe also checks the FP16 and INT8 matrix cores (``--dtypes f16,i8``):
     ``dtypes`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_DTYPES=true`` for every probed notebook."""
@@ -229,14 +237,15 @@ def gpu_probe_dtypes(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
 
 
 def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False,
-                             mx: bool = False, dtypes: bool = False) -> dict:
+                             mx: bool = False, dtypes: bool = False, mx_all: bool = False) -> dict:
     """Init container that proves the pod's GPUs healthy before the notebook starts.
 
     ``odh-gpu-probe`` (``ops/csrc/probe_cli.cpp``, torch-free) runs the bf16 MFMA GEMM checked
     in registers and the HBM3E pattern sweep on every GPU the device plugin gives the pod, and
     with 2+ GPUs reads the xGMI ring between them (``rccl``: plus an RCCL all-reduce over all
     of them, ``--rccl-mib``; ``mx``: plus the FP8 and MXFP4 block-scaled GEMMs checked the same
-    way, ``--mx fp8,fp4``; ``dtypes``: plus the FP16 and INT8 GEMMs, ``--dtypes f16,i8``);
+    way, ``--mx fp8,fp4``; ``mx_all``: that step in all five formats of the instruction,
+    ``--mx fp8,fp4,bf8,fp6,bf6``; ``dtypes``: plus the FP16 and INT8 GEMMs, ``--dtypes f16,i8``);
     non-zero exit keeps the pod in Init, and its JSON verdict is the container's termination message.  It asks for the same
     ``amd.com/gpu`` count as the notebook: the kubelet device manager hands an init
     container's devices on to the app containers, so the GPUs probed are the GPUs the
@@ -245,8 +254,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
     args = ["--json", "/dev/termination-log", "--timeout-ms", env.get("GPU_PROBE_TIMEOUT_MS") or GPU_PROBE_TIMEOUT_MS]
     if rccl:
         args += ["--rccl-mib", GPU_PROBE_RCCL_MIB]
-    if mx:
-        args += ["--mx", GPU_PROBE_MX_FORMATS]
+    if mx or mx_all:
+        args += ["--mx", GPU_PROBE_MX_ALL_FORMATS if mx_all else GPU_PROBE_MX_FORMATS]
     if dtypes:  # after the --mx arguments: every argument list without it stays as it was
         args += ["--dtypes", GPU_PROBE_DTYPES_FORMATS]
     return {
@@ -270,7 +279,7 @@ def _gpu_probe(nb: dict, pod_spec: dict, env: Mapping[str, str]) -> None:
     n = gpu_request(pod_spec)
     # before any init container that uses the GPU
     inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env), mx=gpu_probe_mx(nb, env),
-                                             dtypes=gpu_probe_dtypes(nb, env)))
+                                             dtypes=gpu_probe_dtypes(nb, env), mx_all=gpu_probe_mx_all(nb, env)))
 
 
 def generate_statefulset(nb: dict, is_generate_name: bool, env: Mapping[str, str] = os.environ) -> dict:

@@ -29,6 +29,9 @@ enum {
   // operand formats of the block-scaled (MX) kernels: the hardware's format codes
   ODH_MX_FP8 = 0,  // OCP e4m3fn, one byte per element
   ODH_MX_FP4 = 4,  // e2m1, two elements per byte (even k in the low nibble)
+  ODH_MX_BF8 = 1,  // OCP e5m2, one byte per element
+  ODH_MX_FP6 = 2,  // e2m3, packed: element k in bits [6k, 6k + 6) of the row, little endian
+  ODH_MX_BF6 = 3,  // e3m2, packed as FP6
   ODH_MX_CLASSES = 315,  // floats in the table of expected values: (i mod 15, j mod 21)
   // operand formats of the dense FP16 / INT8 kernels (gpu_probe_dense.h)
   ODH_DT_F16 = 1,  // IEEE half, fp32 accumulation
@@ -80,6 +83,7 @@ int odh_peer_enable(int dev, int peer);
 int odh_busy(float* out, int blocks, int iters, hipStream_t stream);
 // Block-scaled FP8 / MXFP4 (fmt: ODH_MX_*): A [M][K] and Bt [N][K] codes, sA / sBt [rows][K/32] E8M0
 // bytes (4-byte aligned), M and N multiples of 256, K of 64 (FP8) or 128 (FP4); table: ODH_MX_CLASSES floats
+// BF8 as FP8; FP6 / BF6 rows are 3K/4 bytes (32 elements in 24 bytes), K a multiple of 128
 int odh_mx_zero_classes(int K);  // host only: classes expecting 0 at this K (-1: K not a multiple of 128)
 int odh_mx_fill(int fmt, void* A, void* Bt, void* sA, void* sBt, float* table, int M, int N, int K,
                 hipStream_t stream);

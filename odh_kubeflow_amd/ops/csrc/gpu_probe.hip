@@ -30,7 +30,8 @@
 //  * odh_gemm_bf16_256_variant, odh_probe_gemm_verify_2buf / _deep, odh_hbm_write_variant,
 //    odh_hbm_check_variant — A/B entry points (microbenchmarks, kernel numerics tests).
 //  * odh_mx_fill / odh_mx_gemm / odh_mx_probe_gemm_verify — the same exact check on the
-//    block-scaled FP8 / MXFP4 path (v_mfma_scale_f32_32x32x64_f8f6f4; gpu_probe_mx.h), and
+//    block-scaled path in each of its five operand formats, FP8, BF8, FP6, BF6 and MXFP4
+//    (v_mfma_scale_f32_32x32x64_f8f6f4; gpu_probe_mx.h), and
 //    odh_mx_zero_classes, the host-side guard against a K at which that check is blind.
 //  * odh_dense_fill / odh_dense_gemm / odh_dense_probe_gemm_verify — the same exact check on the
 //    FP16 and INT8 paths (v_mfma_f32_32x32x16_f16, v_mfma_i32_32x32x32_i8; gpu_probe_dense.h):
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
   if (ts && lane == 0) ts_end(ts);
 }
 
-#include "gpu_probe_mx.h"  // the FP8 / MXFP4 block-scaled kernels, on the tile helpers above
+#include "gpu_probe_mx.h"  // the block-scaled kernels (FP8, BF8, FP6, BF6, MXFP4), on the tile helpers above
 #include "gpu_probe_dense.h"  // the FP16 / INT8 kernels, on the same helpers and the ring above
 
 __device__ __forceinline__ uint16_t small_int_bf16(int v) {
@@ -1135,7 +1136,7 @@ int odh_const_check(const void* buf, size_t bytes, uint32_t expect, unsigned lon
   return (int)hipGetLastError();
 }
 
-// ------------------------------------------------------------------ FP8 / MXFP4 (gpu_probe_mx.h)
+// ------------------------------------------------------------------ block-scaled formats (gpu_probe_mx.h)
 
 // host only (no HIP call): how many of the 315 (i mod 15, j mod 21) classes expect 0 at this K,
 // where the check cannot tell a right product from an all-zero one; -1 for a K that is not a
@@ -1151,7 +1152,7 @@ int odh_mx_zero_classes(int K) {
 int odh_mx_fill(int fmt, void* A, void* Bt, void* sA, void* sBt, float* table, int M, int N, int K,
                 hipStream_t stream) {
   if (!mx_ok(fmt, M, N, K) || !A || !Bt || !sA || !sBt || !table) return (int)hipErrorInvalidValue;
-  const size_t n = ((size_t)M + N) * (size_t)(K / (fmt == ODH_MX_FP4 ? 2 : 1)) + ((size_t)M + N) * (size_t)(K / 32);
+  const size_t n = ((size_t)M + N) * mx_row_bytes(fmt, K) + ((size_t)M + N) * (size_t)(K / 32);
   mx_fill_kernel<<<grid_for(n, 256), 256, 0, stream>>>(fmt, (uint8_t*)A, (uint8_t*)Bt, (uint8_t*)sA, (uint8_t*)sBt, M,
                                                       N, K);
   hipError_t e = hipGetLastError();
@@ -1164,15 +1165,9 @@ int odh_mx_fill(int fmt, void* A, void* Bt, void* sA, void* sBt, float* table, i
 int odh_mx_gemm(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt, float* C, int M, int N, int K,
                 hipStream_t stream) {
   if (!mx_ok(fmt, M, N, K) || !mx_aligned(A, Bt, sA, sBt) || !C) return (int)hipErrorInvalidValue;
-  const int nwg = gemm256_tiles(M, N);
-  if (fmt == ODH_MX_FP4)
-    mx_gemm256_kernel<ODH_MX_FP4, false><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, C, nullptr, N, K, nullptr, nullptr,
-        nullptr, nullptr);
-  else
-    mx_gemm256_kernel<ODH_MX_FP8, false><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, C, nullptr, N, K, nullptr, nullptr,
-        nullptr, nullptr);
+  mx_launch_gemm<false>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA,
+                        (const uint8_t*)sBt, C, (const float*)nullptr, N, K, (int*)nullptr, (int*)nullptr,
+                        (unsigned*)nullptr, (unsigned*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1182,16 +1177,10 @@ int odh_mx_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void*
                              const float* table, int M, int N, int K, int* tile_xcd, int* counters,
                              hipStream_t stream) {
   if (!mx_ok(fmt, M, N, K) || !mx_aligned(A, Bt, sA, sBt) || !table || !counters) return (int)hipErrorInvalidValue;
-  const int nwg = gemm256_tiles(M, N);
   unsigned* c = (unsigned*)counters;
-  if (fmt == ODH_MX_FP4)
-    mx_gemm256_kernel<ODH_MX_FP4, true><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, nullptr, table, N, K, tile_xcd,
-        counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
-  else
-    mx_gemm256_kernel<ODH_MX_FP8, true><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA, (const uint8_t*)sBt, nullptr, table, N, K, tile_xcd,
-        counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  mx_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA,
+                       (const uint8_t*)sBt, (float*)nullptr, table, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+                       c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

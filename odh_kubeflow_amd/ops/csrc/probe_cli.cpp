@@ -22,7 +22,10 @@
 //      its stream, per format: the probe operands re-encoded as FP8 / MXFP4 codes with E8M0
 //      block scales into the bf16 operands' buffers (odh_mx_fill), then the block-scaled GEMM
 //      (v_mfma_scale_f32_32x32x64_f8f6f4) checked in registers against a 15 × 21 table
-//      (odh_mx_probe_gemm_verify): the data path a quantised model runs on;
+//      (odh_mx_probe_gemm_verify): the data path a quantised model runs on.  The list may name
+//      any of the instruction's five operand formats, fp8,fp4,bf8,fp6,bf6 (the "mxall" notebooks):
+//      BF8 is the gradient format of FP8 training, FP6 and BF6 the MXFP6 formats, whose 6-bit
+//      decode and 96-byte stage rows no other check touches;
 //   6. with --dtypes f16,i8 (the `amd.com/gpu-probe: "dtypes"` notebooks), after the HBM sweep, on
 //      its stream and before step 5, per format: the probe operands re-encoded as halves or as
 //      int8 (odh_dense_fill) into the bf16 operands' buffers, then the FP16
@@ -86,6 +89,9 @@ struct Options {
   int streams = 0;
 };
 
+constexpr int MX_NFMT = 5;  // operand formats of the block-scaled instruction: the longest --mx list
+constexpr int DT_NFMT = 2;  // formats of --dtypes
+
 // device counters: the counter block of gpu_probe.h in its CLI layout
 struct Dev {
   int index = 0;
@@ -105,24 +111,31 @@ struct Dev {
   void *mx_sa = nullptr, *mx_sbt = nullptr;
   float* mx_table = nullptr;
   int* mx_counters = nullptr;
-  int mx_host[2][ODH_NCOUNT] = {};
-  hipEvent_t e_mx0[2] = {}, e_mx1[2] = {};
-  float mx_ms[2] = {};
+  int mx_host[MX_NFMT][ODH_NCOUNT] = {};
+  hipEvent_t e_mx0[MX_NFMT] = {}, e_mx1[MX_NFMT] = {};
+  float mx_ms[MX_NFMT] = {};
   // --dtypes: one counter block (behind the MX ones) and event pair per format
   int* dt_counters = nullptr;
-  int dt_host[2][ODH_NCOUNT] = {};
-  hipEvent_t e_dt0[2] = {}, e_dt1[2] = {};
-  float dt_ms[2] = {};
+  int dt_host[DT_NFMT][ODH_NCOUNT] = {};
+  hipEvent_t e_dt0[DT_NFMT] = {}, e_dt1[DT_NFMT] = {};
+  float dt_ms[DT_NFMT] = {};
   std::string error;
 };
 
-const char* mx_name(int fmt) { return fmt == ODH_MX_FP4 ? "fp4" : "fp8"; }
+const char* mx_name(int fmt) {
+  return fmt == ODH_MX_FP4 ? "fp4" : fmt == ODH_MX_BF8 ? "bf8" : fmt == ODH_MX_FP6 ? "fp6" : fmt == ODH_MX_BF6 ? "bf6" : "fp8";
+}
+int mx_format(const std::string& name) {
+  for (int fmt : {ODH_MX_FP8, ODH_MX_FP4, ODH_MX_BF8, ODH_MX_FP6, ODH_MX_BF6})
+    if (name == mx_name(fmt)) return fmt;
+  return -1;
+}
 const char* dt_name(int fmt) { return fmt == ODH_DT_I8 ? "i8" : "f16"; }
 
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
-               "[--mx fp8,fp4] [--dtypes f16,i8] [--timeout-ms N] [--streams 0|1|2] "
+               "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--timeout-ms N] [--streams 0|1|2] "
                "[--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes] [--quiet]\n",
                argv0);
   return 64;
@@ -163,7 +176,7 @@ bool parse(int argc, char** argv, Options& o) {
       for (size_t at = 0; at <= v.size();) {
         const size_t comma = std::min(v.find(',', at), v.size());
         const std::string name = v.substr(at, comma - at);
-        const int fmt = name == "fp8" ? ODH_MX_FP8 : name == "fp4" ? ODH_MX_FP4 : -1;
+        const int fmt = mx_format(name);
         if (fmt < 0 || std::find(o.mx.begin(), o.mx.end(), fmt) != o.mx.end()) return false;
         o.mx.push_back(fmt);
         at = comma + 1;
@@ -188,7 +201,7 @@ bool parse(int argc, char** argv, Options& o) {
   // the probe operands sum to zero over their period of 35 in k: at K % 35 == 0 the expected
   // product is 0 everywhere and matrix cores that return zeros would pass, so K is refused
   // the all-reduce's send and receive buffers are the two halves of the HBM buffer
-  // --mx: one K for both formats (128 = one FP4 stage), and none of the 315 classes of the MX
+  // --mx: one K for every format (128 = one FP4, FP6 or BF6 stage), and none of the 315 classes of the MX
   // operands may expect 0 at it (odh_mx_zero_classes: host arithmetic, before any HIP call)
   if (!o.mx.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
   if (o.fault == "mx" && o.mx.empty()) return false;
@@ -361,8 +374,14 @@ bool mx_launch(Dev& d, const Options& o, size_t f) {
   HIP_TRY(hipSetDevice(d.index));
   HIP_TRY(odh_mx_fill(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, d.sh));
   if (o.fault == "mx") {
-    // A[0][0] becomes +3 (FP4: A[0][1], the high nibble, is 0): row 0 of C is wrong wherever Bt[j][0] != 0
-    HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_MX_FP4 ? 0x05 : 0x44, 1, d.sh));
+    // A[0][0] becomes +3 (A[0][1] is 0, so byte 0 holds nothing else that is set in FP4's high nibble
+    // or the packed formats' upper two bits): row 0 of C is wrong wherever Bt[j][0] != 0
+    const int three = fmt == ODH_MX_FP4   ? 0x05
+                      : fmt == ODH_MX_BF8 ? 0x42
+                      : fmt == ODH_MX_FP6 ? 0x14
+                      : fmt == ODH_MX_BF6 ? 0x12
+                                          : 0x44;
+    HIP_TRY(hipMemsetAsync(d.a, three, 1, d.sh));
   }
   HIP_TRY(hipEventRecord(d.e_mx0[f], d.sh));
   HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, counters,
@@ -438,9 +457,11 @@ void release(Dev& d) {
   if (d.block) (void)hipFree(d.block);
   for (hipEvent_t e : {d.e0, d.e_gemm, d.e_h0, d.e_h1, d.e_link0, d.e_link1, d.e_r0, d.e_r1})
     if (e) (void)hipEventDestroy(e);
-  for (int f = 0; f < 2; ++f) {
+  for (int f = 0; f < MX_NFMT; ++f) {
     if (d.e_mx0[f]) (void)hipEventDestroy(d.e_mx0[f]);
     if (d.e_mx1[f]) (void)hipEventDestroy(d.e_mx1[f]);
+  }
+  for (int f = 0; f < DT_NFMT; ++f) {
     if (d.e_dt0[f]) (void)hipEventDestroy(d.e_dt0[f]);
     if (d.e_dt1[f]) (void)hipEventDestroy(d.e_dt1[f]);
   }
@@ -670,7 +691,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   const double probe_ms = ms_since(t_probe0);
   // --dtypes, then --mx: one format at a time over every device, so each format has a host time
   // of its own
-  double dt_host_ms[2] = {};
+  double dt_host_ms[DT_NFMT] = {};
   const auto t_dt0 = Clock::now();
   for (size_t f = 0; f < o.dtypes.size(); ++f) {
     const auto t0 = Clock::now();
@@ -681,7 +702,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     dt_host_ms[f] = ms_since(t0);
   }
   const double dt_total_ms = ms_since(t_dt0);
-  double mx_host_ms[2] = {};
+  double mx_host_ms[MX_NFMT] = {};
   const auto t_mx0 = Clock::now();
   for (size_t f = 0; f < o.mx.size(); ++f) {
     const auto t0 = Clock::now();
@@ -790,7 +811,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the object of an optional GEMM step (--mx, --dtypes), "" without it: per format, whatever the
   // device count, total mismatches and the slowest device's kernel time
   auto step_json = [&](const char* key, const std::vector<int>& fmts, const char* (*name)(int), const char* what,
-                       int (Dev::*host)[2][ODH_NCOUNT], float (Dev::*ms)[2], const double* host_ms) {
+                       auto host, auto ms, const double* host_ms) {  // members of Dev: [formats][ODH_NCOUNT], [formats]
     std::string out;
     for (size_t f = 0; f < fmts.size(); ++f) {
       uint64_t errs = 0;

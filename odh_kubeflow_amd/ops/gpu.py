@@ -14,9 +14,10 @@
   since events cannot split a graph launch.  Reports matrix-core TFLOP/s, HBM GB/s,
   mismatches (attributed to the XCD that computed them) and how many of the 8 XCDs ran
   workgroups.
-* :func:`mx_fill`, :func:`mx_gemm`, :func:`mx_probe` — the block-scaled FP8 / MXFP4 path of the
-  matrix cores (``v_mfma_scale_f32_32x32x64_f8f6f4``) on uint8 code tensors: the same exact
-  in-register check, against a 15 × 21 table (``odh-gpu-probe --mx``).
+* :func:`mx_fill`, :func:`mx_gemm`, :func:`mx_probe` — the block-scaled path of the matrix cores
+  (``v_mfma_scale_f32_32x32x64_f8f6f4``) in its five operand formats (FP8, BF8, FP6, BF6, MXFP4)
+  on uint8 code tensors: the same exact in-register check, against a 15 × 21 table
+  (``odh-gpu-probe --mx``).
 * :func:`dense_fill`, :func:`dense_gemm`, :func:`dense_probe` — the FP16 and INT8 paths
   (``v_mfma_f32_32x32x16_f16``, ``v_mfma_i32_32x32x32_i8``) on float16 / int8 tensors: the same
   check against the bf16 probe's 5 × 7 closed form (``odh-gpu-probe --dtypes``).
@@ -65,8 +66,13 @@ ODH_SLOT_GRAPH_SWEEP_SPAN = 24  # 2 × u64
 # operand formats of the block-scaled (MX) kernels: the hardware's format codes
 ODH_MX_FP8 = 0  # OCP e4m3fn, one byte per element
 ODH_MX_FP4 = 4  # e2m1, two elements per byte (even k in the low nibble)
+ODH_MX_BF8 = 1  # OCP e5m2, one byte per element
+ODH_MX_FP6 = 2  # e2m3, packed: element k in bits [6k, 6k + 6) of the row, little endian
+ODH_MX_BF6 = 3  # e3m2, packed as FP6
 ODH_MX_CLASSES = 315  # floats in the table of expected values
-MX_FORMATS = {"fp8": ODH_MX_FP8, "fp4": ODH_MX_FP4}
+MX_FORMATS = {"fp8": ODH_MX_FP8, "fp4": ODH_MX_FP4}  # what ``--mx`` of the "mx" notebooks checks
+MX_EXTRA_FORMATS = {"bf8": ODH_MX_BF8, "fp6": ODH_MX_FP6, "bf6": ODH_MX_BF6}  # the instruction's other three
+MX_ALL_FORMATS = {**MX_FORMATS, **MX_EXTRA_FORMATS}
 MX_TABLE = (15, 21)  # expected values of the MX probe operands, by (i mod 15, j mod 21)
 # operand formats of the dense FP16 / INT8 kernels (csrc/gpu_probe_dense.h)
 ODH_DT_F16 = 1  # IEEE half, fp32 accumulation
@@ -235,15 +241,29 @@ def gemm_bf16(a, bt, out=None, tile_xcd=None, xcd_blocks=None, tile: Optional[in
 
 
 def _mx_format(fmt) -> int:
-    code = MX_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
-    if code not in MX_FORMATS.values():
-        raise ValueError(f"MX format must be one of {sorted(MX_FORMATS)}; got {fmt!r}")
+    code = MX_ALL_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in MX_ALL_FORMATS.values():
+        raise ValueError(f"MX format must be one of {sorted(MX_ALL_FORMATS)}; got {fmt!r}")
     return code
 
 
+def _mx_stage(code: int) -> int:
+    """Elements of a row per stage: 64 bytes of FP8, BF8 or FP4, 96 bytes of FP6 or BF6."""
+    return 64 if code in (ODH_MX_FP8, ODH_MX_BF8) else 128
+
+
+def mx_row_bytes(fmt, k: int) -> int:
+    """Bytes of a row of ``k`` elements in the public layout: one per byte (FP8, BF8), two (FP4),
+    or four in three bytes (FP6, BF6: element k in bits ``[6k, 6k + 6)`` of the row)."""
+    code = _mx_format(fmt)
+    if code in (ODH_MX_FP6, ODH_MX_BF6):
+        return k // 4 * 3
+    return k // 2 if code == ODH_MX_FP4 else k
+
+
 def mx_shape_ok(fmt, m: int, n: int, k: int) -> bool:
-    """256² output tiles, and K in stages of 64 bytes per row: 64 FP8 or 128 FP4 elements."""
-    bk = 128 if _mx_format(fmt) == ODH_MX_FP4 else 64
+    """256² output tiles, and K in whole stages: 64 FP8 or BF8 elements, 128 FP4, FP6 or BF6."""
+    bk = _mx_stage(_mx_format(fmt))
     return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
 
 
@@ -255,7 +275,8 @@ def mx_zero_classes(k: int) -> int:
 
 def _mx_operands(fmt, a, bt, sa, sbt):
     """Checks of the MX entry points, before launch: uint8, one GPU, contiguous, and the public
-    layout (A ``[M, K/epb]``, Bt ``[N, K/epb]`` codes, scales ``[rows, K/32]``).  Returns M, N, K."""
+    layout (A ``[M, row bytes]``, Bt ``[N, row bytes]`` codes, scales ``[rows, K/32]``; row bytes are
+    K, K/2 for FP4, or 3K/4 for FP6 / BF6).  Returns the format code, M, N, K."""
     import torch
 
     code = _mx_format(fmt)
@@ -268,10 +289,17 @@ def _mx_operands(fmt, a, bt, sa, sbt):
         raise ValueError("operands and scales must live on the same GPU")
     if not all(t.is_contiguous() for t in ts):
         raise ValueError("operands and scales must be contiguous")
-    epb = 2 if code == ODH_MX_FP4 else 1
-    m, n, k = a.shape[0], bt.shape[0], a.shape[1] * epb
-    if bt.shape[1] != a.shape[1] or not mx_shape_ok(code, m, n, k):
-        raise ValueError(f"M,N must be multiples of 256 and K of {64 * epb}; got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    row_bytes = a.shape[1]
+    if code in (ODH_MX_FP6, ODH_MX_BF6):  # packed 6-bit: a stage of a row is 96 bytes
+        if row_bytes % 96:
+            raise ValueError(f"rows of packed 6-bit codes are multiples of 96 bytes; got A{tuple(a.shape)}")
+        k = row_bytes * 4 // 3
+    else:
+        k = row_bytes * (2 if code == ODH_MX_FP4 else 1)
+    m, n = a.shape[0], bt.shape[0]
+    if bt.shape[1] != row_bytes or not mx_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {_mx_stage(code)}; "
+                         f"got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
     if tuple(sa.shape) != (m, k // 32) or tuple(sbt.shape) != (n, k // 32):
         raise ValueError(f"scales must be [{m},{k // 32}] and [{n},{k // 32}]; "
                          f"got {tuple(sa.shape)} {tuple(sbt.shape)}")
@@ -279,7 +307,7 @@ def _mx_operands(fmt, a, bt, sa, sbt):
 
 
 def mx_fill(fmt, a, bt, sa, sbt, table) -> None:
-    """The probe operands encoded for ``fmt`` (``"fp8"`` / ``"fp4"``), their E8M0 block scales and
+    """The probe operands encoded for ``fmt`` (a name of :data:`MX_ALL_FORMATS`), their E8M0 block scales and
     the 15 × 21 fp32 table of expected values, written into the given tensors."""
     import torch
 
@@ -334,7 +362,7 @@ def mx_verify(fmt, a, bt, sa, sbt, table) -> dict:
 
 
 def mx_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
-    """One FP8 / MXFP4 probe of a GPU: fill, then the GEMM with the check fused into its
+    """One block-scaled probe of a GPU in any of the five formats: fill, then the GEMM with the check fused into its
     epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
     import torch
 
@@ -342,10 +370,10 @@ def mx_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1],
     if not mx_shape_ok(code, m, n, k):
         raise ValueError("MX probe shape must be tile aligned")
     dev = torch.device("cuda", device)
-    epb = 2 if code == ODH_MX_FP4 else 1
+    rb = mx_row_bytes(code, k)
     with torch.cuda.device(dev):
-        a = torch.empty((m, k // epb), dtype=torch.uint8, device=dev)
-        bt = torch.empty((n, k // epb), dtype=torch.uint8, device=dev)
+        a = torch.empty((m, rb), dtype=torch.uint8, device=dev)
+        bt = torch.empty((n, rb), dtype=torch.uint8, device=dev)
         sa = torch.empty((m, k // 32), dtype=torch.uint8, device=dev)
         sbt = torch.empty((n, k // 32), dtype=torch.uint8, device=dev)
         table = torch.empty(MX_TABLE, dtype=torch.float32, device=dev)
