@@ -1197,13 +1197,8 @@ int odh_dense_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t 
 // C[M][N] = A · Btᵀ for any operands: fp32 out of halves, int32 out of int8
 int odh_dense_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream) {
   if (!dense_ok(fmt, M, N, K) || !dense_aligned(A, Bt) || !C || ((uintptr_t)C & 3)) return (int)hipErrorInvalidValue;
-  const int nwg = gemm256_tiles(M, N);
-  if (fmt == ODH_DT_I8)
-    dense_gemm256_kernel<ODH_DT_I8, false><<<nwg, G_THREADS, 0, stream>>>((const uint4*)A, (const uint4*)Bt, C, N, K,
-                                                                          nullptr, nullptr, nullptr, nullptr);
-  else
-    dense_gemm256_kernel<ODH_DT_F16, false><<<nwg, G_THREADS, 0, stream>>>((const uint4*)A, (const uint4*)Bt, C, N, K,
-                                                                           nullptr, nullptr, nullptr, nullptr);
+  dense_launch_gemm<false>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, C, N, K, (int*)nullptr,
+                           (int*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1212,16 +1207,9 @@ int odh_dense_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N
 int odh_dense_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
                                 int* counters, hipStream_t stream) {
   if (!dense_ok(fmt, M, N, K) || !dense_aligned(A, Bt) || !counters) return (int)hipErrorInvalidValue;
-  const int nwg = gemm256_tiles(M, N);
   unsigned* c = (unsigned*)counters;
-  if (fmt == ODH_DT_I8)
-    dense_gemm256_kernel<ODH_DT_I8, true><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, nullptr, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
-        c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
-  else
-    dense_gemm256_kernel<ODH_DT_F16, true><<<nwg, G_THREADS, 0, stream>>>(
-        (const uint4*)A, (const uint4*)Bt, nullptr, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
-        c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  dense_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (void*)nullptr, N, K,
+                          tile_xcd, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

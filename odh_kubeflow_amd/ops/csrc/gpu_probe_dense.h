@@ -215,6 +215,15 @@ __global__ __launch_bounds__(G_THREADS, 1) void dense_gemm256_kernel(
   }
 }
 
+// both formats' kernel on one argument list
+template <bool VERIFY, typename... Args>
+void dense_launch_gemm(int fmt, int nwg, hipStream_t stream, Args... args) {
+  if (fmt == ODH_DT_I8)
+    dense_gemm256_kernel<ODH_DT_I8, VERIFY><<<nwg, G_THREADS, 0, stream>>>(args...);
+  else
+    dense_gemm256_kernel<ODH_DT_F16, VERIFY><<<nwg, G_THREADS, 0, stream>>>(args...);
+}
+
 // host side: what the dense entry points take
 bool dense_ok(int fmt, int M, int N, int K) {
   return dense_fmt_ok(fmt) && M > 0 && N > 0 && K > 0 && M % G_BM == 0 && N % G_BN == 0 && K % dense_bk(fmt) == 0;

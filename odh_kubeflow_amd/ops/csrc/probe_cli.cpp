@@ -70,6 +70,56 @@ double ms_since(Clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
 }
 
+struct Dev;
+struct Options;
+
+// what one asked-for format of an optional GEMM step keeps on one device
+struct Slot {
+  int* counters = nullptr;  // its counter block on the device
+  int host[ODH_NCOUNT] = {};
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0;
+};
+
+// An optional GEMM step (--mx, --dtypes): per asked-for format, the probe operands re-encoded into
+// the bf16 operands' buffers and a fused check of that format's matrix-core instruction.
+struct Step {
+  const char* word;  // the option (--word), the --inject-fault word and the verdict key
+  const char* what;  // in the error string: "<N> <what> mismatches"
+  std::vector<std::pair<const char*, int>> formats;  // name <-> code
+  // one format on one device, on the sweep's stream: fill, the fault if asked for, event, fused
+  // verify, event, the counters copied back
+  bool (*run)(Dev&, const Options&, int fmt, Slot&);
+  std::vector<int> asked = {};  // the formats to check, in the order given
+
+  const char* name(int fmt) const {
+    for (const auto& nf : formats)
+      if (nf.second == fmt) return nf.first;
+    return "?";
+  }
+  // a comma list of formats, each at most once
+  bool ask(const std::string& v) {
+    for (size_t at = 0; at <= v.size();) {
+      const size_t comma = std::min(v.find(',', at), v.size());
+      const std::string name = v.substr(at, comma - at);
+      int fmt = -1;
+      for (const auto& nf : formats)
+        if (name == nf.first) fmt = nf.second;
+      if (fmt < 0 || std::find(asked.begin(), asked.end(), fmt) != asked.end()) return false;
+      asked.push_back(fmt);
+      at = comma + 1;
+    }
+    return true;
+  }
+};
+
+bool mx_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
+
+// the steps in the verdict's order, which is also the order of their counter blocks and events;
+// they run the other way round, --dtypes before --mx
+enum { STEP_MX, STEP_DTYPES, N_STEPS };
+
 struct Options {
   int M = 4096, N = 4096, K = 1024;
   size_t hbm_bytes = 256ull << 20;
@@ -77,9 +127,13 @@ struct Options {
   size_t rccl_bytes = 0;  // 0: no RCCL step
   long timeout_ms = 30000;
   std::string json_path;  // "" = default; "-" = stdout only
-  std::string fault;      // test hook: gemm | hbm | xgmi | rccl | mx | dtypes
-  std::vector<int> mx;    // --mx: ODH_MX_* formats to check, in the order given
-  std::vector<int> dtypes;  // --dtypes: ODH_DT_* formats to check, in the order given
+  std::string fault;      // test hook: gemm | hbm | xgmi | rccl | a step's word
+  Step steps[N_STEPS] = {
+      {"mx", "MX GEMM",
+       {{"fp8", ODH_MX_FP8}, {"fp4", ODH_MX_FP4}, {"bf8", ODH_MX_BF8}, {"fp6", ODH_MX_FP6}, {"bf6", ODH_MX_BF6}},
+       mx_run},
+      {"dtypes", "GEMM", {{"f16", ODH_DT_F16}, {"i8", ODH_DT_I8}}, dt_run},  // tflops counts integer operations for i8
+  };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
   // 1 = one stream, 2 = the HBM sweep overlapping the GEMM on a second stream.  Each stream is
@@ -88,9 +142,6 @@ struct Options {
   // overlapping the sweep saves 0.005 ms of GPU time and halves both measured rates (pass r6_g9)
   int streams = 0;
 };
-
-constexpr int MX_NFMT = 5;  // operand formats of the block-scaled instruction: the longest --mx list
-constexpr int DT_NFMT = 2;  // formats of --dtypes
 
 // device counters: the counter block of gpu_probe.h in its CLI layout
 struct Dev {
@@ -107,30 +158,12 @@ struct Dev {
   float gemm_ms = 0, hbm_ms = 0, link_ms = 0, rccl_ms = 0;
   double malloc_ms = 0, streams_ms = 0, events_ms = 0, first_op_ms = 0;  // host-side set-up, step by step
   int link_source = -1;
-  // --mx: scales and table behind the counters, one counter block and event pair per format
+  // --mx: scales and table behind the counters
   void *mx_sa = nullptr, *mx_sbt = nullptr;
   float* mx_table = nullptr;
-  int* mx_counters = nullptr;
-  int mx_host[MX_NFMT][ODH_NCOUNT] = {};
-  hipEvent_t e_mx0[MX_NFMT] = {}, e_mx1[MX_NFMT] = {};
-  float mx_ms[MX_NFMT] = {};
-  // --dtypes: one counter block (behind the MX ones) and event pair per format
-  int* dt_counters = nullptr;
-  int dt_host[DT_NFMT][ODH_NCOUNT] = {};
-  hipEvent_t e_dt0[DT_NFMT] = {}, e_dt1[DT_NFMT] = {};
-  float dt_ms[DT_NFMT] = {};
+  std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
   std::string error;
 };
-
-const char* mx_name(int fmt) {
-  return fmt == ODH_MX_FP4 ? "fp4" : fmt == ODH_MX_BF8 ? "bf8" : fmt == ODH_MX_FP6 ? "fp6" : fmt == ODH_MX_BF6 ? "bf6" : "fp8";
-}
-int mx_format(const std::string& name) {
-  for (int fmt : {ODH_MX_FP8, ODH_MX_FP4, ODH_MX_BF8, ODH_MX_FP6, ODH_MX_BF6})
-    if (name == mx_name(fmt)) return fmt;
-  return -1;
-}
-const char* dt_name(int fmt) { return fmt == ODH_DT_I8 ? "i8" : "f16"; }
 
 int usage(const char* argv0) {
   std::fprintf(stderr,
@@ -170,31 +203,16 @@ bool parse(int argc, char** argv, Options& o) {
       if (o.streams < 0 || o.streams > 2) return false;
     } else if (a == "--inject-fault") {
       o.fault = v;
-      if (v != "gemm" && v != "hbm" && v != "xgmi" && v != "rccl" && v != "mx" && v != "dtypes") return false;
-    } else if (a == "--mx") {
-      // a comma list of formats, each at most once
-      for (size_t at = 0; at <= v.size();) {
-        const size_t comma = std::min(v.find(',', at), v.size());
-        const std::string name = v.substr(at, comma - at);
-        const int fmt = mx_format(name);
-        if (fmt < 0 || std::find(o.mx.begin(), o.mx.end(), fmt) != o.mx.end()) return false;
-        o.mx.push_back(fmt);
-        at = comma + 1;
-      }
-    } else if (a == "--dtypes") {
-      // the same kind of list
-      for (size_t at = 0; at <= v.size();) {
-        const size_t comma = std::min(v.find(',', at), v.size());
-        const std::string name = v.substr(at, comma - at);
-        const int fmt = name == "f16" ? ODH_DT_F16 : name == "i8" ? ODH_DT_I8 : -1;
-        if (fmt < 0 || std::find(o.dtypes.begin(), o.dtypes.end(), fmt) != o.dtypes.end()) return false;
-        o.dtypes.push_back(fmt);
-        at = comma + 1;
-      }
+      bool known = v == "gemm" || v == "hbm" || v == "xgmi" || v == "rccl";
+      for (const Step& s : o.steps) known = known || v == s.word;
+      if (!known) return false;
     } else if (a == "--quiet") {
       o.quiet = true;
     } else {
-      return false;
+      Step* step = nullptr;
+      for (Step& s : o.steps)
+        if (a == std::string("--") + s.word) step = &s;
+      if (!step || !step->ask(v)) return false;
     }
   }
   // the fused check needs 256² output tiles and K in 64-element steps
@@ -203,11 +221,12 @@ bool parse(int argc, char** argv, Options& o) {
   // the all-reduce's send and receive buffers are the two halves of the HBM buffer
   // --mx: one K for every format (128 = one FP4, FP6 or BF6 stage), and none of the 315 classes of the MX
   // operands may expect 0 at it (odh_mx_zero_classes: host arithmetic, before any HIP call)
-  if (!o.mx.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
-  if (o.fault == "mx" && o.mx.empty()) return false;
+  if (!o.steps[STEP_MX].asked.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
   // --dtypes: the operands are the bf16 probe's (times constants for i8), so the K rules below
   // cover it: K % 64 == 0 is a whole number of f16 and of i8 stages, K % 35 != 0 a non-zero product
-  if (o.fault == "dtypes" && o.dtypes.empty()) return false;
+  // a step's fault needs the step
+  for (const Step& s : o.steps)
+    if (o.fault == s.word && s.asked.empty()) return false;
   return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 && o.K % 35 != 0 &&
          o.hbm_bytes >= (1u << 20) && o.timeout_ms > 0 && 2 * o.rccl_bytes <= o.hbm_bytes &&
          (o.fault != "rccl" || o.rccl_bytes > 0);
@@ -270,9 +289,11 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t na = align_up((size_t)o.M * o.K * 2), nb = align_up((size_t)o.N * o.K * 2);
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
-  // --mx adds a counter block per format behind the first, the scales of both operands and the table
-  // --dtypes adds one more per format behind those, and nothing else: its operands are no larger
-  const size_t nmx = o.mx.size(), ndt = o.dtypes.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nmx + ndt));
+  // every optional step adds a counter block per format behind the first; --mx also the scales of both
+  // operands and the table, --dtypes nothing else: its operands are no larger
+  size_t nslots = 0;
+  for (const Step& s : o.steps) nslots += s.asked.size();
+  const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
   HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab));
@@ -284,12 +305,15 @@ bool setup_alloc(Dev& d, const Options& o) {
   d.tile_xcd = (int*)(p + na + nb + nh);
   d.counters = (int*)(p + na + nb + nh + nt);
   if (nmx) {
-    d.mx_counters = d.counters + ODH_NCOUNT;
     d.mx_sa = p + na + nb + nh + nt + nc;
     d.mx_sbt = p + na + nb + nh + nt + nc + nsa;
     d.mx_table = (float*)(p + na + nb + nh + nt + nc + nsa + nsb);
   }
-  if (ndt) d.dt_counters = d.counters + ODH_NCOUNT * (1 + nmx);
+  int* block = d.counters;
+  for (int s = 0; s < N_STEPS; ++s) {
+    d.slots[s].resize(o.steps[s].asked.size());
+    for (Slot& slot : d.slots[s]) slot.counters = block += ODH_NCOUNT;
+  }
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -298,19 +322,16 @@ bool setup_alloc(Dev& d, const Options& o) {
   t0 = Clock::now();
   for (hipEvent_t* e : {&d.e0, &d.e_gemm, &d.e_h0, &d.e_h1, &d.e_link0, &d.e_link1, &d.e_r0, &d.e_r1})
     HIP_TRY(hipEventCreate(e));
-  for (size_t f = 0; f < nmx; ++f) {
-    HIP_TRY(hipEventCreate(&d.e_mx0[f]));
-    HIP_TRY(hipEventCreate(&d.e_mx1[f]));
-  }
-  for (size_t f = 0; f < ndt; ++f) {
-    HIP_TRY(hipEventCreate(&d.e_dt0[f]));
-    HIP_TRY(hipEventCreate(&d.e_dt1[f]));
-  }
+  for (auto& slots : d.slots)
+    for (Slot& slot : slots) {
+      HIP_TRY(hipEventCreate(&slot.e0));
+      HIP_TRY(hipEventCreate(&slot.e1));
+    }
   d.events_ms = ms_since(t0);
   // the first operation on the stream: on the null stream it creates the hardware queue, here
   // while the other thread is still loading the code object
   t0 = Clock::now();
-  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nmx + ndt), d.sg));
+  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nslots), d.sg));
   d.first_op_ms = ms_since(t0);
   return true;
 }
@@ -366,11 +387,9 @@ bool finish(Dev& d) {
   return true;
 }
 
-// format f of --mx on the sweep's stream, after the sweep: the operands re-encoded into the bf16
-// operands' buffers (that GEMM is done, and the codes are no larger), then the fused check
-bool mx_launch(Dev& d, const Options& o, size_t f) {
-  const int fmt = o.mx[f];
-  int* counters = d.mx_counters + f * ODH_NCOUNT;
+// a format of --mx, after the sweep: the operands re-encoded into the bf16 operands' buffers (that
+// GEMM is done, and the codes are no larger) with their scales and the table, then the fused check
+bool mx_run(Dev& d, const Options& o, int fmt, Slot& s) {
   HIP_TRY(hipSetDevice(d.index));
   HIP_TRY(odh_mx_fill(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, d.sh));
   if (o.fault == "mx") {
@@ -383,27 +402,17 @@ bool mx_launch(Dev& d, const Options& o, size_t f) {
                                           : 0x44;
     HIP_TRY(hipMemsetAsync(d.a, three, 1, d.sh));
   }
-  HIP_TRY(hipEventRecord(d.e_mx0[f], d.sh));
-  HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, counters,
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, s.counters,
                                    d.sh));
-  HIP_TRY(hipEventRecord(d.e_mx1[f], d.sh));
-  HIP_TRY(hipMemcpyAsync(d.mx_host[f], counters, sizeof d.mx_host[f], hipMemcpyDeviceToHost, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
 }
 
-bool mx_finish(Dev& d, size_t f) {
-  HIP_TRY(hipSetDevice(d.index));
-  HIP_TRY(hipStreamSynchronize(d.sh));
-  HIP_TRY(hipEventElapsedTime(&d.mx_ms[f], d.e_mx0[f], d.e_mx1[f]));
-  return true;
-}
-
-// format f of --dtypes on the sweep's stream, after the sweep and before --mx: the operands
-// re-encoded into the bf16 operands' buffers (halves are as large, int8 half as large), then the
-// fused check
-bool dt_launch(Dev& d, const Options& o, size_t f) {
-  const int fmt = o.dtypes[f];
-  int* counters = d.dt_counters + f * ODH_NCOUNT;
+// a format of --dtypes, after the sweep and before --mx: the operands re-encoded into the bf16
+// operands' buffers (halves are as large, int8 half as large), then the fused check
+bool dt_run(Dev& d, const Options& o, int fmt, Slot& s) {
   HIP_TRY(hipSetDevice(d.index));
   HIP_TRY(odh_dense_fill(fmt, d.a, d.bt, o.M, o.N, o.K, d.sh));
   if (o.fault == "dtypes") {
@@ -416,17 +425,17 @@ bool dt_launch(Dev& d, const Options& o, size_t f) {
       HIP_TRY(hipMemsetAsync((char*)d.a + 1, 0x3C, 1, d.sh));
     }
   }
-  HIP_TRY(hipEventRecord(d.e_dt0[f], d.sh));
-  HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, counters, d.sh));
-  HIP_TRY(hipEventRecord(d.e_dt1[f], d.sh));
-  HIP_TRY(hipMemcpyAsync(d.dt_host[f], counters, sizeof d.dt_host[f], hipMemcpyDeviceToHost, d.sh));
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
 }
 
-bool dt_finish(Dev& d, size_t f) {
+bool step_finish(Dev& d, Slot& s) {
   HIP_TRY(hipSetDevice(d.index));
   HIP_TRY(hipStreamSynchronize(d.sh));
-  HIP_TRY(hipEventElapsedTime(&d.dt_ms[f], d.e_dt0[f], d.e_dt1[f]));
+  HIP_TRY(hipEventElapsedTime(&s.ms, s.e0, s.e1));
   return true;
 }
 
@@ -457,14 +466,10 @@ void release(Dev& d) {
   if (d.block) (void)hipFree(d.block);
   for (hipEvent_t e : {d.e0, d.e_gemm, d.e_h0, d.e_h1, d.e_link0, d.e_link1, d.e_r0, d.e_r1})
     if (e) (void)hipEventDestroy(e);
-  for (int f = 0; f < MX_NFMT; ++f) {
-    if (d.e_mx0[f]) (void)hipEventDestroy(d.e_mx0[f]);
-    if (d.e_mx1[f]) (void)hipEventDestroy(d.e_mx1[f]);
-  }
-  for (int f = 0; f < DT_NFMT; ++f) {
-    if (d.e_dt0[f]) (void)hipEventDestroy(d.e_dt0[f]);
-    if (d.e_dt1[f]) (void)hipEventDestroy(d.e_dt1[f]);
-  }
+  for (auto& slots : d.slots)
+    for (Slot& slot : slots)
+      for (hipEvent_t e : {slot.e0, slot.e1})
+        if (e) (void)hipEventDestroy(e);
   if (d.sh && d.sh != d.sg) (void)hipStreamDestroy(d.sh);
   if (d.sg) (void)hipStreamDestroy(d.sg);
 }
@@ -691,28 +696,22 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   const double probe_ms = ms_since(t_probe0);
   // --dtypes, then --mx: one format at a time over every device, so each format has a host time
   // of its own
-  double dt_host_ms[DT_NFMT] = {};
-  const auto t_dt0 = Clock::now();
-  for (size_t f = 0; f < o.dtypes.size(); ++f) {
-    const auto t0 = Clock::now();
-    for (Dev& d : devs)
-      if (!dt_launch(d, o, f)) return fail_all(d);
-    for (Dev& d : devs)
-      if (!dt_finish(d, f)) return fail_all(d);
-    dt_host_ms[f] = ms_since(t0);
+  std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
+  double step_total_ms[N_STEPS] = {};
+  for (int si : {STEP_DTYPES, STEP_MX}) {
+    const Step& s = o.steps[si];
+    step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
+    const auto t_step0 = Clock::now();
+    for (size_t f = 0; f < s.asked.size(); ++f) {
+      const auto t0 = Clock::now();
+      for (Dev& d : devs)
+        if (!s.run(d, o, s.asked[f], d.slots[si][f])) return fail_all(d);
+      for (Dev& d : devs)
+        if (!step_finish(d, d.slots[si][f])) return fail_all(d);
+      step_host_ms[si][f] = ms_since(t0);
+    }
+    step_total_ms[si] = ms_since(t_step0);
   }
-  const double dt_total_ms = ms_since(t_dt0);
-  double mx_host_ms[MX_NFMT] = {};
-  const auto t_mx0 = Clock::now();
-  for (size_t f = 0; f < o.mx.size(); ++f) {
-    const auto t0 = Clock::now();
-    for (Dev& d : devs)
-      if (!mx_launch(d, o, f)) return fail_all(d);
-    for (Dev& d : devs)
-      if (!mx_finish(d, f)) return fail_all(d);
-    mx_host_ms[f] = ms_since(t0);
-  }
-  const double mx_total_ms = ms_since(t_mx0);
   // xGMI ring: device r reads the pattern device r-1 wrote (2 GPUs: each reads the other)
   const auto t_link0 = Clock::now();
   if (ndev >= 2) {
@@ -808,17 +807,19 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                   ndev > 1 ? algbw * 2.0 * (ndev - 1) / ndev : algbw);
     rccl = b;
   }
-  // the object of an optional GEMM step (--mx, --dtypes), "" without it: per format, whatever the
-  // device count, total mismatches and the slowest device's kernel time
-  auto step_json = [&](const char* key, const std::vector<int>& fmts, const char* (*name)(int), const char* what,
-                       auto host, auto ms, const double* host_ms) {  // members of Dev: [formats][ODH_NCOUNT], [formats]
-    std::string out;
-    for (size_t f = 0; f < fmts.size(); ++f) {
+  // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
+  // total mismatches and the slowest device's kernel time
+  std::string steps;
+  char step_timing[96] = "";
+  for (int si = 0; si < N_STEPS; ++si) {
+    const Step& s = o.steps[si];
+    for (size_t f = 0; f < s.asked.size(); ++f) {
       uint64_t errs = 0;
       float slowest = 0;
       bool fok = true;
       for (Dev& d : devs) {
-        const int* h = (d.*host)[f];
+        const Slot& slot = d.slots[si][f];
+        const int* h = slot.host;
         long blocks = 0;
         std::string where;
         for (int x = 0; x < ODH_N_XCD; ++x) {
@@ -827,35 +828,30 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
         }
         const uint32_t e = (uint32_t)h[ODH_SLOT_GEMM_ERR];
         errs += e;
-        slowest = (d.*ms)[f] > slowest ? (d.*ms)[f] : slowest;
+        slowest = slot.ms > slowest ? slot.ms : slowest;
         if (e == 0 && blocks == tiles) continue;
         fok = false;
         if (first_err.empty()) {
           char b[200];
-          std::snprintf(b, sizeof b, "GPU %d: %s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index, name(fmts[f]), e,
-                        what, where.empty() ? "-" : where.c_str(), blocks, tiles);
+          std::snprintf(b, sizeof b, "GPU %d: %s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index,
+                        s.name(s.asked[f]), e, s.what, where.empty() ? "-" : where.c_str(), blocks, tiles);
           first_err = b;
         }
       }
       ok = ok && fok;
       char b[128];
       std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"tflops\":%.1f,\"host_ms\":%.3f}",
-                    f ? "," : (std::string(",\"") + key + "\":{").c_str(), name(fmts[f]), fok ? "true" : "false",
-                    (unsigned long long)errs, slowest, slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, host_ms[f]);
-      out += b;
+                    f ? "," : (std::string(",\"") + s.word + "\":{").c_str(), s.name(s.asked[f]),
+                    fok ? "true" : "false", (unsigned long long)errs, slowest,
+                    slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, step_host_ms[si][f]);
+      steps += b;
     }
-    return out.empty() ? out : out + "}";
-  };
-  const std::string mx = step_json("mx", o.mx, mx_name, "MX GEMM", &Dev::mx_host, &Dev::mx_ms, mx_host_ms);
-  // tflops counts integer operations for i8
-  const std::string dt = step_json("dtypes", o.dtypes, dt_name, "GEMM", &Dev::dt_host, &Dev::dt_ms, dt_host_ms);
-  for (Dev& d : devs) release(d);
-  char step_timing[96] = "";
-  if (!o.mx.empty()) std::snprintf(step_timing, sizeof step_timing, "\"mx\":%.3f,", mx_total_ms);
-  if (!o.dtypes.empty()) {
+    if (s.asked.empty()) continue;
+    steps += "}";
     const size_t at = std::strlen(step_timing);
-    std::snprintf(step_timing + at, sizeof step_timing - at, "\"dtypes\":%.3f,", dt_total_ms);
+    std::snprintf(step_timing + at, sizeof step_timing - at, "\"%s\":%.3f,", s.word, step_total_ms[si]);
   }
+  for (Dev& d : devs) release(d);
   char tail[512];
   std::snprintf(tail, sizeof tail,
                 ",\"timings_ms\":{\"exec\":%.3f,\"hip_init\":%.3f,\"alloc_fill\":%.3f,\"alloc\":%.3f,"
@@ -870,6 +866,6 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                      ",\"shape\":[" + std::to_string(o.M) + "," + std::to_string(o.N) + "," + std::to_string(o.K) +
                      "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
                      (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
-                     ",\"links\":" + links + rccl + mx + dt + setup + tail;
+                     ",\"links\":" + links + rccl + steps + setup + tail;
   return done(ok ? 0 : 1, json);
 }

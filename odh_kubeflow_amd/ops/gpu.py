@@ -247,18 +247,28 @@ def _mx_format(fmt) -> int:
     return code
 
 
+# The public layout of a row, by format code: elements per stage of the kernel, and row bytes as a
+# fraction (numerator, denominator) of K.  One element per byte (FP8, BF8), two (FP4), or four in
+# three bytes (FP6, BF6: element k in bits ``[6k, 6k + 6)`` of the row): a stage of a row is 64
+# bytes, or 96 of the packed 6-bit formats.
+_MX_LAYOUT = {
+    ODH_MX_FP8: (64, 1, 1),
+    ODH_MX_BF8: (64, 1, 1),
+    ODH_MX_FP4: (128, 1, 2),
+    ODH_MX_FP6: (128, 3, 4),
+    ODH_MX_BF6: (128, 3, 4),
+}
+
+
 def _mx_stage(code: int) -> int:
-    """Elements of a row per stage: 64 bytes of FP8, BF8 or FP4, 96 bytes of FP6 or BF6."""
-    return 64 if code in (ODH_MX_FP8, ODH_MX_BF8) else 128
+    """Elements of a row per stage."""
+    return _MX_LAYOUT[code][0]
 
 
 def mx_row_bytes(fmt, k: int) -> int:
-    """Bytes of a row of ``k`` elements in the public layout: one per byte (FP8, BF8), two (FP4),
-    or four in three bytes (FP6, BF6: element k in bits ``[6k, 6k + 6)`` of the row)."""
-    code = _mx_format(fmt)
-    if code in (ODH_MX_FP6, ODH_MX_BF6):
-        return k // 4 * 3
-    return k // 2 if code == ODH_MX_FP4 else k
+    """Bytes of a row of ``k`` elements in the public layout."""
+    _, num, den = _MX_LAYOUT[_mx_format(fmt)]
+    return k // den * num
 
 
 def mx_shape_ok(fmt, m: int, n: int, k: int) -> bool:
@@ -273,6 +283,42 @@ def mx_zero_classes(k: int) -> int:
     return load_library().odh_mx_zero_classes(k)
 
 
+def _same_gpu_2d(family: str, what: str, dtype, dtype_error: str, *ts) -> None:
+    """What every MX and dense entry point asks of its tensors before launch: ``dtype``, 2-D, one
+    GPU, contiguous."""
+    if any(t.dtype != dtype for t in ts):
+        raise TypeError(dtype_error)
+    if any(t.dim() != 2 for t in ts):
+        raise ValueError(f"{family} {what} are 2-D")
+    if not all(t.is_cuda and t.device == ts[0].device for t in ts):
+        raise ValueError(f"{what} must live on the same GPU")
+    if not all(t.is_contiguous() for t in ts):
+        raise ValueError(f"{what} must be contiguous")
+
+
+def _fused_check(dev, m: int, n: int, k: int, launch) -> dict:
+    """A fused check on a fresh counter block, and its report.  ``launch(tile_xcd, counters, stream)``
+    is the one kernel launch; its time is taken with events around it."""
+    import torch
+
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
+        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(launch(tile_xcd.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    ms = e0.elapsed_time(e1)
+    return {
+        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
+        "ms": ms, "tflops": 2.0 * m * n * k / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
+    }
+
+
 def _mx_operands(fmt, a, bt, sa, sbt):
     """Checks of the MX entry points, before launch: uint8, one GPU, contiguous, and the public
     layout (A ``[M, row bytes]``, Bt ``[N, row bytes]`` codes, scales ``[rows, K/32]``; row bytes are
@@ -280,25 +326,15 @@ def _mx_operands(fmt, a, bt, sa, sbt):
     import torch
 
     code = _mx_format(fmt)
-    ts = (a, bt, sa, sbt)
-    if any(t.dtype != torch.uint8 for t in ts):
-        raise TypeError("MX operands and scales are uint8 codes")
-    if any(t.dim() != 2 for t in ts):
-        raise ValueError("MX operands and scales are 2-D")
-    if not all(t.is_cuda and t.device == a.device for t in ts):
-        raise ValueError("operands and scales must live on the same GPU")
-    if not all(t.is_contiguous() for t in ts):
-        raise ValueError("operands and scales must be contiguous")
+    _same_gpu_2d("MX", "operands and scales", torch.uint8, "MX operands and scales are uint8 codes", a, bt, sa, sbt)
+    stage, num, den = _MX_LAYOUT[code]
     row_bytes = a.shape[1]
-    if code in (ODH_MX_FP6, ODH_MX_BF6):  # packed 6-bit: a stage of a row is 96 bytes
-        if row_bytes % 96:
-            raise ValueError(f"rows of packed 6-bit codes are multiples of 96 bytes; got A{tuple(a.shape)}")
-        k = row_bytes * 4 // 3
-    else:
-        k = row_bytes * (2 if code == ODH_MX_FP4 else 1)
-    m, n = a.shape[0], bt.shape[0]
+    m, n, k = a.shape[0], bt.shape[0], row_bytes * den // num
+    if num != 1 and row_bytes % (stage * num // den):  # packed 6-bit: a stage of a row is 96 bytes
+        raise ValueError(f"rows of packed 6-bit codes are multiples of {stage * num // den} bytes; "
+                         f"got A{tuple(a.shape)}")
     if bt.shape[1] != row_bytes or not mx_shape_ok(code, m, n, k):
-        raise ValueError(f"M,N must be multiples of 256 and K of {_mx_stage(code)}; "
+        raise ValueError(f"M,N must be multiples of 256 and K of {stage}; "
                          f"got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
     if tuple(sa.shape) != (m, k // 32) or tuple(sbt.shape) != (n, k // 32):
         raise ValueError(f"scales must be [{m},{k // 32}] and [{n},{k // 32}]; "
@@ -337,28 +373,13 @@ def mx_gemm(fmt, a, bt, sa, sbt, out=None):
 def mx_verify(fmt, a, bt, sa, sbt, table) -> dict:
     """The fused check of the given operands against ``table`` on a fresh counter block; the
     kernel's time is taken with events around its one launch."""
-    import torch
-
     code, m, n, k = _mx_operands(fmt, a, bt, sa, sbt)
-    dev = a.device
-    with torch.cuda.device(dev):
-        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
-        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _check(load_library().odh_mx_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), sa.data_ptr(),
-                                                       sbt.data_ptr(), table.data_ptr(), m, n, k, tile_xcd.data_ptr(),
-                                                       counters.data_ptr(), _stream_ptr(dev)))
-        e1.record()
-        e1.synchronize()
-        h = counters.cpu().tolist()
-    ms = e0.elapsed_time(e1)
-    return {
-        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
-        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
-        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
-        "ms": ms, "tflops": 2.0 * m * n * k / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
-    }
+
+    def launch(tile_xcd, counters, stream):
+        return load_library().odh_mx_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), sa.data_ptr(), sbt.data_ptr(),
+                                                       table.data_ptr(), m, n, k, tile_xcd, counters, stream)
+
+    return _fused_check(a.device, m, n, k, launch)
 
 
 def mx_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
@@ -400,15 +421,8 @@ def _dense_operands(fmt, a, bt):
     import torch
 
     code = _dense_format(fmt)
-    want = torch.int8 if code == ODH_DT_I8 else torch.float16
-    if a.dtype != want or bt.dtype != want:
-        raise TypeError(f"{'i8' if code == ODH_DT_I8 else 'f16'} operands are {want}")
-    if a.dim() != 2 or bt.dim() != 2:
-        raise ValueError("dense operands are 2-D")
-    if not (a.is_cuda and bt.is_cuda) or a.device != bt.device:
-        raise ValueError("operands must live on the same GPU")
-    if not (a.is_contiguous() and bt.is_contiguous()):
-        raise ValueError("operands must be contiguous")
+    name, want = ("i8", torch.int8) if code == ODH_DT_I8 else ("f16", torch.float16)
+    _same_gpu_2d("dense", "operands", want, f"{name} operands are {want}", a, bt)
     m, k = a.shape
     n = bt.shape[0]
     if bt.shape[1] != k or not dense_shape_ok(code, m, n, k):
@@ -444,27 +458,13 @@ def dense_verify(fmt, a, bt) -> dict:
     """The fused check of the given operands against the closed form on a fresh counter block;
     the kernel's time is taken with events around its one launch.  The dict of :func:`mx_verify`
     (``tflops`` counts integer operations for ``"i8"``)."""
-    import torch
-
     code, m, n, k = _dense_operands(fmt, a, bt)
-    dev = a.device
-    with torch.cuda.device(dev):
-        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
-        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _check(load_library().odh_dense_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), m, n, k,
-                                                          tile_xcd.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
-        e1.record()
-        e1.synchronize()
-        h = counters.cpu().tolist()
-    ms = e0.elapsed_time(e1)
-    return {
-        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
-        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
-        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
-        "ms": ms, "tflops": 2.0 * m * n * k / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
-    }
+
+    def launch(tile_xcd, counters, stream):
+        return load_library().odh_dense_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), m, n, k, tile_xcd,
+                                                          counters, stream)
+
+    return _fused_check(a.device, m, n, k, launch)
 
 
 def dense_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:

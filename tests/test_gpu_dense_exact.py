@@ -9,49 +9,23 @@ data only; every pointer handed to a kernel comes from a torch allocation of exa
 the shape implies.
 """
 
-import faulthandler
 import functools
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import probe_reference as ref
+from probe_gpu import NP_DTYPE, _gpu, _run_probe
+from probe_gpu import _own_timeout, dev  # noqa: F401  (fixtures)
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
 FORMATS = ["f16", "i8"]
-TEST_TIMEOUT_S = 60  # per test: a hung kernel ends the run here instead of holding the GPU
-NP_DTYPE = {"f16": np.float16, "i8": np.int8}
 EXACT_BELOW = {"f16": 2 ** 24, "i8": 2 ** 31}
 I8_MUL_A, I8_MUL_B = 25, 41
-
-
-@pytest.fixture(autouse=True)
-def _own_timeout():
-    faulthandler.dump_traceback_later(TEST_TIMEOUT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X")
-    from odh_kubeflow_amd.ops import gpu
-
-    gpu.load_library()  # loud failure if the in-tree .so is missing
-    return torch.device("cuda", 0)
-
-
-def _gpu():
-    from odh_kubeflow_amd.ops import gpu
-
-    return gpu
 
 
 def _stage(fmt):
@@ -261,19 +235,6 @@ def test_dense_probe_reports_the_check(dev):
 
 
 # ------------------------------------------------------------------ the program
-
-
-def _run_probe(*args, timeout=120):
-    from odh_kubeflow_amd.ops import probe_main
-
-    exe = probe_main.executable()
-    if not os.path.exists(exe):
-        pytest.fail("odh-gpu-probe not built: python -m odh_kubeflow_amd.ops.build")
-    env = {k: v for k, v in os.environ.items() if not k.startswith(("HIP_VISIBLE", "ROCR_VISIBLE", "CUDA_VISIBLE"))}
-    env["HIP_VISIBLE_DEVICES"] = "0"
-    r = subprocess.run(["timeout", "-k", "10", str(timeout), exe, "--json", "-", *args], capture_output=True,
-                       text=True, env=env, timeout=timeout + 20)
-    return r.returncode, probe_main.parse_result(r.stdout), r
 
 
 def _check_formats_pass(block, names):

@@ -1,6 +1,7 @@
-"""Sweeps of the four low-precision probe kernels on a real MI355X: ``mx_gemm256_kernel<FP8|FP4>``
+"""Sweeps of the low-precision probe kernels on a real MI355X: ``mx_gemm256_kernel<FP8|FP4>``
 (``gpu_probe_mx.h``) and ``dense_gemm256_kernel<F16|I8>`` (``gpu_probe_dense.h``), held to the
-standard of the bf16 sweep of ``test_gpu_kernels_exact.py``.
+standard of the bf16 sweep of ``test_gpu_kernels_exact.py``.  The sweep and store checks are those
+of ``probe_gpu.py``; ``test_gpu_mx_formats_exact.py`` runs them on BF8, FP6 and BF6.
 
 * The fused check: one operand element per row and per column, and one scale byte per row and
   per column, is changed, launch by launch, at 2 × 2 tiles and several stages.  Every launch must
@@ -16,230 +17,30 @@ from a torch allocation of exactly the size the shape implies (a launch's counte
 map are rows of such an allocation).
 """
 
-import faulthandler
-import functools
-import types
-
 import numpy as np
 import pytest
 
-import mx_reference as mx
 import probe_reference as ref
+from probe_gpu import _assert_operands_are_the_models, _assert_store_exact, _gpu, _probe
+from probe_gpu import store_applies_every_scale_byte, store_decodes_every_code, sweep_every_row_and_column
+from probe_gpu import sweep_every_scale_byte
+from probe_gpu import _own_timeout, dev  # noqa: F401  (fixtures)
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
-MX_FORMATS = ["fp8", "fp4"]
-FORMATS = ["fp8", "fp4", "f16", "i8"]
-TEST_TIMEOUT_S = 60  # per test: a hung kernel ends the run here instead of holding the GPU
-NP_DTYPE = {"f16": np.float16, "i8": np.int8}
-I8_MUL = {"a": 25, "bt": 41}
-# 2 × 2 tiles, so tm and tn are both non-zero somewhere.  fp8 / fp4: 6 and 3 stages, odd and even
-# stages on both buffers, no class expecting 0; f16 / i8: 5 stages, so the ring is refilled
-SWEEP_SHAPE = {"fp8": (512, 512, 384), "fp4": (512, 512, 384), "f16": (512, 512, 160), "i8": (512, 512, 320)}
-
-
-@pytest.fixture(autouse=True)
-def _own_timeout():
-    faulthandler.dump_traceback_later(TEST_TIMEOUT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X")
-    from odh_kubeflow_amd.ops import gpu
-
-    gpu.load_library()  # loud failure if the in-tree .so is missing
-    return torch.device("cuda", 0)
-
-
-def _gpu():
-    from odh_kubeflow_amd.ops import gpu
-
-    return gpu
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-# ------------------------------------------------------------------ the probe operands and their model
-
-
-def _wrap_i8(x):
-    return ((np.asarray(x, dtype=np.int64) + 128) % 256 - 128).astype(np.int8)
-
-
-@functools.lru_cache(maxsize=None)
-def _probe(fmt, m, n, k):
-    """The probe operands of ``fmt`` on the GPU (written by the library's fill and compared with
-    the model once), the model's copies on the host, the expected C, a ``product(host)`` that
-    multiplies host operands in float64 / int64, and a ``launch(tile_xcd_ptr, counters_ptr)`` of
-    the fused check.  Shared between tests: every test leaves the operands as it found them."""
-    gpu = _gpu()
-    lib = gpu.load_library()
-    dev = torch.device("cuda", 0)
-    p = types.SimpleNamespace(fmt=fmt, m=m, n=n, k=k, device=dev)
-    if fmt in MX_FORMATS:
-        code = mx.NAMES[fmt]
-        epb = 2 if fmt == "fp4" else 1
-        t = {"a": torch.full((m, k // epb), 0xEE, dtype=torch.uint8, device=dev),
-             "bt": torch.full((n, k // epb), 0xEE, dtype=torch.uint8, device=dev),
-             "sa": torch.zeros((m, k // 32), dtype=torch.uint8, device=dev),
-             "sbt": torch.zeros((n, k // 32), dtype=torch.uint8, device=dev)}
-        table = torch.full(gpu.MX_TABLE, float("nan"), device=dev)
-        gpu.mx_fill(fmt, t["a"], t["bt"], t["sa"], t["sbt"], table)
-        p.values = mx.probe_values(m, n, k)
-        p.host = {"a": mx.encode(code, p.values[0]), "bt": mx.encode(code, p.values[1]),
-                  "sa": mx.probe_scales(m, k), "sbt": mx.probe_scales(n, k)}
-        p.expect = mx.probe_table(k)[np.arange(m)[:, None] % mx.ROWS, np.arange(n)[None, :] % mx.COLS]
-        assert np.array_equal(table.cpu().double().numpy(), mx.probe_table(k))
-        p.product = lambda h: mx.product(code, h["a"], h["bt"], h["sa"], h["sbt"])
-
-        def launch(tile_xcd, counters):
-            gpu._check(lib.odh_mx_probe_gemm_verify(code, t["a"].data_ptr(), t["bt"].data_ptr(), t["sa"].data_ptr(),
-                                                    t["sbt"].data_ptr(), table.data_ptr(), m, n, k, tile_xcd,
-                                                    counters, _stream(dev)))
-    else:
-        code = gpu.DENSE_FORMATS[fmt]
-        dtype = torch.int8 if fmt == "i8" else torch.float16
-        t = {"a": torch.full((m, k), 77, dtype=dtype, device=dev), "bt": torch.full((n, k), 77, dtype=dtype, device=dev)}
-        gpu.dense_fill(fmt, t["a"], t["bt"])
-        va, vb = ref.probe_operands(m, n, k)
-        mul = (gpu.ODH_DT_I8_MUL_A, gpu.ODH_DT_I8_MUL_B) if fmt == "i8" else (1, 1)
-        assert fmt != "i8" or mul == (I8_MUL["a"], I8_MUL["bt"])
-        p.values = (va * mul[0], vb * mul[1])
-        p.host = {"a": p.values[0].astype(NP_DTYPE[fmt]), "bt": p.values[1].astype(NP_DTYPE[fmt])}
-        p.expect = (ref.probe_class_table(k) * mul[0] * mul[1])[np.arange(m)[:, None] % 5, np.arange(n)[None, :] % 7]
-        wide = np.int64 if fmt == "i8" else np.float64  # float64 holds the halves' inf and NaN too
-        p.product = lambda h: h["a"].astype(wide) @ h["bt"].astype(wide).T
-
-        def launch(tile_xcd, counters):
-            gpu._check(lib.odh_dense_probe_gemm_verify(code, t["a"].data_ptr(), t["bt"].data_ptr(), m, n, k,
-                                                       tile_xcd, counters, _stream(dev)))
-    p.t, p.launch = t, launch
-    _assert_operands_are_the_models(p)
-    # the model agrees with itself: the clean product is the table, so a launch's mismatches are
-    # exactly those of the one line its corrupted element touches
-    assert np.array_equal(p.product(p.host), p.expect)
-    return p
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint8)
-
-
-def _assert_operands_are_the_models(p):
-    for name, host in p.host.items():
-        assert np.array_equal(_bits(p.t[name].cpu().numpy()), _bits(host)), f"{p.fmt} {name} differs from the model"
-
-
-def _sweep(p, name, wrong_host, rows):
-    """``wrong_host`` is the model's ``name`` (``a``, ``bt``, ``sa`` or ``sbt``) with one element
-    of every row changed.  Launch x runs with only row x's element changed, into counter row x
-    and tile map x, and restores it; everything is read back once at the end.
-
-    A changed element of row i of A (or of its scales) changes only row i of the product, so row
-    i of the product of ``wrong_host`` with the other, clean operands is launch i's row i, and
-    every other row of that launch is clean.  For Bt and its scales the same holds of columns."""
-    gpu = _gpu()
-    m, n = p.m, p.n
-    tiles_m, tiles_n = m // 256, n // 256
-    tiles = tiles_m * tiles_n
-    count = m if rows else n
-    target, clean_host = p.t[name], p.host[name]
-    assert (name in ("a", "sa")) == rows and wrong_host.shape == clean_host.shape == (count, target.shape[1])
-    diff = np.argwhere(wrong_host != clean_host)
-    assert np.array_equal(diff[:, 0], np.arange(count)), "one changed element per row"
-    offs = (diff[:, 0] * target.shape[1] + diff[:, 1]).tolist()
-    dev = p.device
-    wrong = torch.from_numpy(wrong_host[diff[:, 0], diff[:, 1]]).to(dev)
-    clean = torch.from_numpy(clean_host[diff[:, 0], diff[:, 1]]).to(dev)
-    tflat = target.view(-1)
-    counters = torch.zeros((count, gpu.ODH_NCOUNT), dtype=torch.int32, device=dev)
-    tile_xcd = torch.full((count, tiles), -1, dtype=torch.int32, device=dev)
-    cp, tp = counters.data_ptr(), tile_xcd.data_ptr()
-    try:
-        for x in range(count):
-            tflat[offs[x]:offs[x] + 1].copy_(wrong[x:x + 1])
-            p.launch(tp + 4 * tiles * x, cp + 4 * gpu.ODH_NCOUNT * x)
-            tflat[offs[x]:offs[x] + 1].copy_(clean[x:x + 1])
-    finally:
-        tflat[torch.tensor(offs, device=dev)] = clean  # the operands are shared between tests
-    h = counters.cpu().numpy()
-    tx = tile_xcd.cpu().numpy()
-    _assert_operands_are_the_models(p)
-
-    mismatch = p.product(dict(p.host, **{name: wrong_host})) != p.expect  # [i][j]
-    lines = mismatch if rows else mismatch.T  # [x][position along launch x's line]
-    want_err = lines.sum(axis=1)
-    assert (want_err > 0).all(), "a launch that expects no mismatch checks nothing"
-    per_tile = lines.reshape(count, -1, 256).sum(axis=2)  # [x][tile along the line]
-    assert ((tx >= 0) & (tx < gpu.N_XCD)).all(), tx[((tx < 0) | (tx >= gpu.N_XCD)).any(axis=1)][:4]
-    want_xcd = np.zeros((count, gpu.N_XCD), dtype=np.int64)
-    for x in range(count):
-        for t in range(per_tile.shape[1]):
-            tm, tn = (x // 256, t) if rows else (t, x // 256)
-            want_xcd[x, tx[x, tm * tiles_n + tn]] += per_tile[x, t]
-    what = f"{p.fmt} {name} " + ("row" if rows else "column")
-    got_err = h[:, gpu.ODH_SLOT_GEMM_ERR].astype(np.int64) & 0xFFFFFFFF
-    for x in np.flatnonzero(got_err != want_err)[:8]:
-        print(f"{what} {x}: {got_err[x]} mismatches counted, {want_err[x]} expected")
-    assert np.array_equal(got_err, want_err), f"{what}s {np.flatnonzero(got_err != want_err)[:16].tolist()}"
-    got_xcd = h[:, gpu.ODH_SLOT_ERR_XCD:gpu.ODH_SLOT_ERR_XCD + gpu.N_XCD]
-    bad = np.flatnonzero((got_xcd != want_xcd).any(axis=1))
-    assert bad.size == 0, f"{what} {bad[0]}: per-XCD {got_xcd[bad[0]].tolist()} != {want_xcd[bad[0]].tolist()}"
-    blocks = h[:, gpu.ODH_SLOT_XCD_BLOCKS:gpu.ODH_SLOT_XCD_BLOCKS + gpu.N_XCD]
-    hist = np.stack([np.bincount(r, minlength=gpu.N_XCD) for r in tx])
-    assert np.array_equal(blocks, hist) and (blocks.sum(axis=1) == tiles).all()
-    return want_err
+MX_FORMATS = ["fp8", "fp4"]  # BF8, FP6 and BF6 run the same sweeps in test_gpu_mx_formats_exact.py
+FORMATS = MX_FORMATS + ["f16", "i8"]
 
 
 # ------------------------------------------------------------------ 1. every row and column
 
 
-def _value_plus_one(p, rows):
-    """The model's A (or Bt) with ``A[i][i % K]`` (``Bt[j][j % K]``) one value higher, re-encoded:
-    -1 .. 3 and -2 .. 4 stay exact in all four formats (FP4 has 3 and 4).  For i8 one higher means
-    plus the multiplier, 25 or 41; ``Bt = 3 · 41 + 41 = 164`` does not fit and wraps to -92, and
-    the model multiplies the int8 that is stored.  The FP4 neighbour nibble is re-encoded
-    unchanged with it."""
-    v = p.values[0 if rows else 1].copy()
-    idx = np.arange(v.shape[0])
-    name = "a" if rows else "bt"
-    if p.fmt in MX_FORMATS:
-        v[idx, idx % p.k] += 1
-        wrong = mx.encode(mx.NAMES[p.fmt], v)
-        if p.fmt == "fp4":  # only the one nibble changed
-            x = (wrong ^ p.host[name])[idx, (idx % p.k) // 2]
-            shift = 4 * ((idx % p.k) & 1)
-            assert ((x >> shift) & 15).all() and not ((x >> (4 - shift)) & 15).any()
-        return name, wrong
-    if p.fmt == "i8":
-        v[idx, idx % p.k] += I8_MUL[name]
-        return name, _wrap_i8(v)
-    v[idx, idx % p.k] += 1
-    return name, v.astype(np.float16)
-
-
 @pytest.mark.parametrize("rows", [True, False], ids=["rows", "columns"])
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_fused_check_sees_every_row_and_column(dev, fmt, rows):
-    """One operand element per launch, 512 launches.  With the probe operands a changed row is
-    wrong in 438 or 439 of 512 columns and a changed column in 409 or 410 of 512 rows (the zeros
-    of the other operand at that k are not), so a check that skips a register, a wave, a
-    fragment or a tile, or books a tile on another XCD, miscounts some launch."""
-    p = _probe(fmt, *SWEEP_SHAPE[fmt])
-    if fmt in MX_FORMATS:
-        assert mx.zero_classes(p.k) == 0
-    else:
-        assert p.k % ref.PERIOD != 0
-    want = _sweep(p, *_value_plus_one(p, rows), rows)
-    assert set(want.tolist()) <= ({438, 439} if rows else {409, 410})
+    sweep_every_row_and_column(fmt, rows)
 
 
 # ------------------------------------------------------------------ 2. every scale byte position
@@ -248,17 +49,7 @@ def test_fused_check_sees_every_row_and_column(dev, fmt, rows):
 @pytest.mark.parametrize("rows", [True, False], ids=["rows", "columns"])
 @pytest.mark.parametrize("fmt", MX_FORMATS)
 def test_fused_check_reads_every_scale_byte(dev, fmt, rows):
-    """``sA[i][i % (K/32)]`` (``sBt[j][j % (K/32)]``) goes up by one, which doubles that block.  The
-    12 blocks of a row are every scale byte of a stage (2 for FP8, 4 for FP4), both lane halves
-    and both ``opsel`` bytes, in every row of the tile."""
-    p = _probe(fmt, *SWEEP_SHAPE[fmt])
-    name = "sa" if rows else "sbt"
-    wrong = p.host[name].copy()
-    idx = np.arange(wrong.shape[0])
-    assert wrong.shape[1] == 12
-    wrong[idx, idx % 12] += 1
-    want = _sweep(p, name, wrong, rows)
-    assert want.min() >= (438 if rows else 409) and want.max() <= 512  # of the model: no launch is vacuous
+    sweep_every_scale_byte(fmt, rows)
 
 
 # ------------------------------------------------------------------ 3. NaN and inf are counted
@@ -311,48 +102,19 @@ def test_fused_check_counts_nan_and_inf(dev, fmt, bits):
 # ------------------------------------------------------------------ 4. store kernels: code against code
 
 
-def _assert_store_exact(what, got, want):
-    """NaN exactly where the model has NaN, equal by value elsewhere (-0 equals 0).  ``got`` was
-    pre-filled with +inf, which no case expects, so an element never stored fails too."""
-    got = got.astype(np.float64)
-    nan = np.isnan(want)
-    wrong = np.where(nan, ~np.isnan(got), got != want)
-    if wrong.any():
-        bad = np.argwhere(wrong)
-        rows, cols = np.unique(bad[:, 0]), np.unique(bad[:, 1])
-        for i, j in bad[:8]:
-            print(f"{what}: C[{i}][{j}] = {got[i, j]!r}, expected {want[i, j]!r}")
-        pytest.fail(f"{what}: {len(bad)} wrong elements in {len(rows)} rows "
-                    f"{[hex(r) for r in rows[:40]]} and {len(cols)} columns {[hex(c) for c in cols[:40]]}")
-
-
-def _mx_store(dev, fmt, case):
-    a, bt, sa, sbt, want = case
-    c = torch.full(want.shape, float("inf"), device=dev)
-    _gpu().mx_gemm(fmt, *[torch.from_numpy(x).to(dev) for x in (a, bt, sa, sbt)], out=c)
-    return c.cpu().numpy(), want
-
-
 @pytest.mark.parametrize("fmt", MX_FORMATS)
 def test_mx_store_decodes_every_code_against_every_code(dev, fmt):
-    """All 256 × 256 pairs of FP8 codes (subnormals, fractional mantissas, ±448 and the two NaN
-    codes included), or all 16 × 16 pairs of FP4 codes sixteen times over, under seeded scales
-    2^-8 .. 2^8: each output is one product, ``decode(i) · decode(j) · 2^(sA + sBt - 254)``."""
-    got, want = _mx_store(dev, fmt, mx.all_codes_case(mx.NAMES[fmt]))
-    _assert_store_exact(f"{fmt} code i × code j", got, want)
+    store_decodes_every_code(dev, fmt)
 
 
 def test_mx_store_applies_every_scale_byte(dev):
-    """E8M0 bytes 1 .. 254: 1.0 · 1.0 under ``sA = i`` and an ``sBt`` that brings the pair back
-    to 2^-20 .. 2^20; every output is that power of two."""
-    got, want = _mx_store(dev, "fp8", mx.e8m0_range_case())
-    _assert_store_exact("fp8 scale i", got, want)
+    store_applies_every_scale_byte(dev, "fp8")
 
 
 def test_f16_store_multiplies_every_value_by_every_value(dev):
     """256 halves — the integers, ±65504, the smallest normal, ±0, all-ones mantissas and random
     normals — against each other: each output one product, exact in fp32."""
     a, bt, want = ref.f16_onehot_case()
-    c = torch.full(want.shape, float("inf"), dtype=torch.float32, device=dev)
+    c = torch.full(want.shape, 3e38, dtype=torch.float32, device=dev)
     _gpu().dense_gemm("f16", torch.from_numpy(a).to(dev), torch.from_numpy(bt).to(dev), out=c)
     _assert_store_exact("f16 value i × value j", c.cpu().numpy(), want)

@@ -5,7 +5,7 @@
 * ``odh-gpu-probe --mx``: its usage errors and the no-GPU verdict;
 * ``odh_mx_zero_classes`` (host arithmetic in the library, through ctypes) against the numpy
   model of ``mx_reference.py``;
-* the model itself: the decoders on known codes, and the closed-form table against the full
+* the model itself: the decoder on known FP8 and FP4 codes, and the closed-form table against the full
   product of the decoded, scaled operands.
 """
 
@@ -128,17 +128,18 @@ def test_zero_classes_match_the_model():
 
 def test_format_constants():
     assert (gpu.ODH_MX_FP8, gpu.ODH_MX_FP4) == (ref.FP8, ref.FP4) == (0, 4)
-    assert gpu.MX_FORMATS == ref.NAMES and gpu.MX_TABLE == (ref.ROWS, ref.COLS)
+    assert gpu.MX_FORMATS == {name: ref.NAMES[name] for name in ("fp8", "fp4")} and gpu.MX_ALL_FORMATS == ref.NAMES
+    assert gpu.MX_TABLE == (ref.ROWS, ref.COLS)
 
 
 # ------------------------------------------------------------------ the model
 
 
 def test_decoders_on_known_codes():
-    assert ref.decode_fp8([0x00, 0x38, 0x40, 0x44, 0xC4, 0x7E, 0x01, 0x08]).tolist() == \
+    assert ref.decode_codes(ref.FP8, [0x00, 0x38, 0x40, 0x44, 0xC4, 0x7E, 0x01, 0x08]).tolist() == \
         [0.0, 1.0, 2.0, 3.0, -3.0, 448.0, 2.0 ** -9, 2.0 ** -6]
-    assert np.isnan(ref.decode_fp8([0x7F, 0xFF])).all()
-    assert ref.decode_fp4([0x05, 0x21, 0xF7]).tolist() == [3.0, 0.0, 0.5, 1.0, 6.0, -6.0]
+    assert np.isnan(ref.decode_codes(ref.FP8, [0x7F, 0xFF])).all()
+    assert ref.decode(ref.FP4, [0x05, 0x21, 0xF7]).tolist() == [3.0, 0.0, 0.5, 1.0, 6.0, -6.0]
     assert ref.scale_values([126, 127, 130]).tolist() == [0.5, 1.0, 8.0]
     fp4 = np.concatenate([-ref.FP4_VALUES[:0:-1], ref.FP4_VALUES])
     for fmt, vals in ((ref.FP8, np.arange(-8.0, 9.0)), (ref.FP4, fp4)):
@@ -196,7 +197,7 @@ def test_all_codes_case_is_exact_in_fp32(fmt):
     for s in (2.0 ** 16, 2.0 ** -16):
         assert np.array_equal((fin * s).astype(np.float32).astype(np.float64), fin * s)
     if fmt == ref.FP8:  # all 254² finite pairs are there, each a product of the decoded codes
-        d = ref.decode_fp8(np.arange(256))
+        d = ref.code_values(ref.FP8)
         assert np.isfinite(d).sum() == 254 and fin.size == 254 * 254
         e = np.log2(np.abs(want[0x38, 0x38]))
         assert e == int(e) and -16 <= e <= 16  # 1.0 · 1.0 · the two scales

@@ -3,7 +3,7 @@
 * the controller: the ``mxall`` token of ``amd.com/gpu-probe`` and ``GPU_PROBE_MX_ALL``, with every
   value accepted before producing the arguments it produced;
 * ``odh-gpu-probe --mx`` with the new names: its usage errors and the no-GPU verdict;
-* the host model (``mx_formats_reference.py``): the decoders on known codes, the 6-bit packing,
+* the host model (``mx_reference.py``): the decoder on known codes of the three formats, the 6-bit packing,
   and the probe's 15 × 21 table against the full product of the operands as each format
   encodes them;
 * the ctypes mirror of the new constants.
@@ -19,8 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import mx_formats_reference as ref
-import mx_reference as mx
+import mx_reference as ref
 from odh_kubeflow_amd.controllers import notebook as nbc
 from odh_kubeflow_amd.controllers.notebook import (GPU_PROBE_ANNOTATION, GPU_PROBE_CONTAINER, generate_statefulset)
 from odh_kubeflow_amd.models.notebook import notebook
@@ -157,9 +156,9 @@ def test_constants_mirror_the_header_and_the_model():
                       "ODH_MX_CLASSES": 315}
     for name, value in header.items():
         assert getattr(gpu, name) == value, name
-    assert gpu.MX_EXTRA_FORMATS == ref.NAMES == {"bf8": 1, "fp6": 2, "bf6": 3}
-    assert gpu.MX_FORMATS == mx.NAMES == {"fp8": 0, "fp4": 4}
-    assert gpu.MX_ALL_FORMATS == {**mx.NAMES, **ref.NAMES}
+    assert gpu.MX_EXTRA_FORMATS == {name: ref.NAMES[name] for name in FORMATS} == {"bf8": 1, "fp6": 2, "bf6": 3}
+    assert gpu.MX_FORMATS == {name: ref.NAMES[name] for name in ("fp8", "fp4")} == {"fp8": 0, "fp4": 4}
+    assert gpu.MX_ALL_FORMATS == ref.NAMES
     assert (ref.BF8, ref.FP6, ref.BF6) == (gpu.ODH_MX_BF8, gpu.ODH_MX_FP6, gpu.ODH_MX_BF6)
     # shapes: K in stages of 64 (BF8) or 128 (FP6, BF6) elements; rows of 3K/4 bytes when packed
     assert gpu.mx_shape_ok("bf8", 256, 512, 64) and not gpu.mx_shape_ok("bf8", 256, 512, 32)
@@ -177,23 +176,23 @@ def test_constants_mirror_the_header_and_the_model():
 
 def _codes():
     """The format codes the library takes, which are the model's."""
-    assert gpu.MX_EXTRA_FORMATS == ref.NAMES
+    assert gpu.MX_EXTRA_FORMATS == {name: ref.NAMES[name] for name in FORMATS}
     return gpu.ODH_MX_BF8, gpu.ODH_MX_FP6, gpu.ODH_MX_BF6
 
 
 def test_decoders_on_known_codes():
     assert _codes() == (ref.BF8, ref.FP6, ref.BF6)
     # the probe's codes of 1, 2, 3 and the sign bit, as the fill encodes them
-    assert ref.decode_bf8([0x00, 0x3C, 0x40, 0x42, 0xC2, 0x80]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
-    assert ref.decode_fp6([0x00, 0x08, 0x10, 0x14, 0x34, 0x20]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
-    assert ref.decode_bf6([0x00, 0x0C, 0x10, 0x12, 0x32, 0x20]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
+    assert ref.decode_codes(ref.BF8, [0x00, 0x3C, 0x40, 0x42, 0xC2, 0x80]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
+    assert ref.decode_codes(ref.FP6, [0x00, 0x08, 0x10, 0x14, 0x34, 0x20]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
+    assert ref.decode_codes(ref.BF6, [0x00, 0x0C, 0x10, 0x12, 0x32, 0x20]).tolist() == [0.0, 1.0, 2.0, 3.0, -3.0, -0.0]
     # the maxima, the smallest subnormals, and e5m2's infinities and NaNs
-    assert ref.decode_bf8([0x7B, 0xFB, 0x01, 0x04]).tolist() == [57344.0, -57344.0, 2.0 ** -16, 2.0 ** -14]
-    assert ref.decode_bf8([0x7C, 0xFC]).tolist() == [np.inf, -np.inf]
-    assert np.isnan(ref.decode_bf8([0x7D, 0x7E, 0x7F, 0xFD, 0xFE, 0xFF])).all()
-    assert np.isfinite(ref.decode_bf8(np.arange(0x7C))).all()
-    assert ref.decode_fp6([0x1F, 0x3F, 0x01, 0x07, 0x09]).tolist() == [7.5, -7.5, 0.125, 0.875, 1.125]
-    assert ref.decode_bf6([0x1F, 0x3F, 0x01, 0x03, 0x04, 0x0D]).tolist() == [28.0, -28.0, 2.0 ** -4, 0.1875, 0.25, 1.25]
+    assert ref.decode_codes(ref.BF8, [0x7B, 0xFB, 0x01, 0x04]).tolist() == [57344.0, -57344.0, 2.0 ** -16, 2.0 ** -14]
+    assert ref.decode_codes(ref.BF8, [0x7C, 0xFC]).tolist() == [np.inf, -np.inf]
+    assert np.isnan(ref.decode_codes(ref.BF8, [0x7D, 0x7E, 0x7F, 0xFD, 0xFE, 0xFF])).all()
+    assert np.isfinite(ref.decode_codes(ref.BF8, np.arange(0x7C))).all()
+    assert ref.decode_codes(ref.FP6, [0x1F, 0x3F, 0x01, 0x07, 0x09]).tolist() == [7.5, -7.5, 0.125, 0.875, 1.125]
+    assert ref.decode_codes(ref.BF6, [0x1F, 0x3F, 0x01, 0x03, 0x04, 0x0D]).tolist() == [28.0, -28.0, 2.0 ** -4, 0.1875, 0.25, 1.25]
     for fmt, top in ((ref.FP6, 7.5), (ref.BF6, 28.0)):
         v = ref.code_values(fmt)
         assert np.isfinite(v).all() and v.max() == top and v.min() == -top
@@ -260,8 +259,8 @@ def test_table_is_the_product_of_the_encoded_operands(fmt, k):
     sa, sbt = ref.probe_scales(m, k), ref.probe_scales(n, k)
     t = ref.probe_table(k)
     want = ref.product(code, a, bt, sa, sbt)
-    assert np.array_equal(want, t[np.arange(m)[:, None] % mx.ROWS, np.arange(n)[None, :] % mx.COLS])
-    assert (mx.zero_classes(k) == 0) == bool((t != 0).all())
+    assert np.array_equal(want, t[np.arange(m)[:, None] % ref.ROWS, np.arange(n)[None, :] % ref.COLS])
+    assert (ref.zero_classes(k) == 0) == bool((t != 0).all())
 
 
 def test_one_hot_cases_are_single_products():
@@ -283,7 +282,7 @@ def test_one_hot_cases_are_single_products():
             assert np.array_equal(codes[np.arange(256), hot], (np.arange(256) + 21 * (np.arange(256) >> 7)) % 64)
             assert (codes != 0).sum(axis=1).max() == 1 and not nan.any()
             assert set(codes[np.arange(256), hot].tolist()) == set(range(64))
-    a, bt, sa, sbt, want = ref.e8m0_range_case()
+    a, bt, sa, sbt, want = ref.e8m0_range_case(ref.FP6)
     assert a.shape == (256, 6144) and set(sa[0].tolist()) == set(range(1, 255))
     assert np.array_equal(ref.unpack6(a)[np.arange(256), 32 * np.arange(256)], np.full(256, 0x08))
     assert np.array_equal(np.log2(want), np.round(np.log2(want))) and want.min() >= 2.0 ** -20
