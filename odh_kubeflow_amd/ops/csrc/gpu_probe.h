@@ -38,6 +38,13 @@ enum {
   ODH_DT_I8 = 2,   // int8, int32 accumulation
   ODH_DT_I8_MUL_A = 25,  // the i8 probe operands: these odd multiples of the bf16 probe's A ...
   ODH_DT_I8_MUL_B = 41,  // ... and Bt, so the expected product is 1025 × the bf16 probe's
+  // operand formats of the FP32 / FP64 kernels (gpu_probe_fp.h): the codes are the element sizes
+  ODH_FP_F32 = 4,  // float, fp32 accumulation
+  ODH_FP_F64 = 8,  // double, fp64 accumulation
+  ODH_FP_F32_MUL_A = 25,  // the f32 probe operands: the i8 probe's multiples of the bf16 probe's A ...
+  ODH_FP_F32_MUL_B = 41,  // ... and Bt: 1025 × the bf16 probe's product, exact in fp32 while 6150 K < 2^24
+  ODH_FP_F64_MUL_A = 1048573,  // the f64 probe operands: odd 20-bit multiples ...
+  ODH_FP_F64_MUL_B = 1048575,  // ... whose products toggle 41 mantissa bits; exact in fp64 at K <= 1365
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -99,6 +106,14 @@ int odh_dense_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t 
 int odh_dense_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream);
 int odh_dense_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
                                 int* counters, hipStream_t stream);
+// FP32 / FP64 (fmt: ODH_FP_*): A [M][K] and Bt [N][K] floats or doubles (16-byte aligned), C [M][N] in the same
+// type; M and N multiples of 256, K of 16 (f32) or 8 (f64); counters as for the dense kernels.  odh_fp_fill and
+// odh_fp_probe_gemm_verify refuse a K at which the probe operands' sums are no longer exact integers
+int odh_fp_tiles(int fmt, int M, int N);  // workgroups the kernels launch: 256×256 (f32) or 256×128 (f64) tiles (0: bad shape)
+int odh_fp_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t stream);
+int odh_fp_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream);
+int odh_fp_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
+                             int* counters, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

@@ -36,6 +36,9 @@
 //  * odh_dense_fill / odh_dense_gemm / odh_dense_probe_gemm_verify — the same exact check on the
 //    FP16 and INT8 paths (v_mfma_f32_32x32x16_f16, v_mfma_i32_32x32x32_i8; gpu_probe_dense.h):
 //    the deep-pipelined 256² tile again, with halves or int8 in its 64-byte stage rows.
+//  * odh_fp_fill / odh_fp_gemm / odh_fp_probe_gemm_verify — the same exact check on the FP32 and
+//    FP64 paths (v_mfma_f32_32x32x2_f32, v_mfma_f64_16x16x4_f64; gpu_probe_fp.h): the ring again, with
+//    floats or doubles in its 64-byte stage rows and a 256×128 tile for f64 (odh_fp_tiles).
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -582,6 +585,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
 
 #include "gpu_probe_mx.h"  // the block-scaled kernels (FP8, BF8, FP6, BF6, MXFP4), on the tile helpers above
 #include "gpu_probe_dense.h"  // the FP16 / INT8 kernels, on the same helpers and the ring above
+#include "gpu_probe_fp.h"  // the FP32 / FP64 kernels, on the same helpers and the ring's constants
 
 __device__ __forceinline__ uint16_t small_int_bf16(int v) {
   // exact for |v| < 256: take the high half of the f32 bit pattern
@@ -1210,6 +1214,42 @@ int odh_dense_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, i
   unsigned* c = (unsigned*)counters;
   dense_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (void*)nullptr, N, K,
                           tile_xcd, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ FP32 / FP64 (gpu_probe_fp.h)
+
+// workgroups (= tiles) the fp kernels launch: 256×256 tiles for f32, 256×128 for f64 (0: bad shape)
+int odh_fp_tiles(int fmt, int M, int N) {
+  return fp_fmt_ok(fmt) && M > 0 && N > 0 && M % G_BM == 0 && N % G_BN == 0 ? fp_tiles(fmt, M, N) : 0;
+}
+
+// the probe operands as floats or doubles, times ODH_FP_*_MUL_A / _B
+int odh_fp_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t stream) {
+  if (!fp_ok(fmt, M, N, K) || !fp_k_exact(fmt, K) || !dense_aligned(A, Bt)) return (int)hipErrorInvalidValue;
+  const size_t n = ((size_t)M + N) * (size_t)K;
+  fp_fill_kernel<<<grid_for(n, 256), 256, 0, stream>>>(fmt, A, Bt, M, N, K);
+  return (int)hipGetLastError();
+}
+
+// C[M][N] = A · Btᵀ for any operands, in the operands' type
+int odh_fp_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream) {
+  if (!fp_ok(fmt, M, N, K) || !dense_aligned(A, Bt) || !C || ((uintptr_t)C & (uintptr_t)(fmt - 1)))
+    return (int)hipErrorInvalidValue;
+  fp_launch_gemm<false>(fmt, fp_tiles(fmt, M, N), stream, (const uint4*)A, (const uint4*)Bt, C, N, K, (int*)nullptr,
+                        (int*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// the same tiles on odh_fp_fill's operands with the check against the closed form fused into the
+// epilogue; counters is a counter block of this format's own
+int odh_fp_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
+                             int* counters, hipStream_t stream) {
+  if (!fp_ok(fmt, M, N, K) || !fp_k_exact(fmt, K) || !dense_aligned(A, Bt) || !counters)
+    return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  fp_launch_gemm<true>(fmt, fp_tiles(fmt, M, N), stream, (const uint4*)A, (const uint4*)Bt, (void*)nullptr, N, K,
+                       tile_xcd, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

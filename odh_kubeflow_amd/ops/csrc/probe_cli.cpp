@@ -30,7 +30,12 @@
 //      its stream and before step 5, per format: the probe operands re-encoded as halves or as
 //      int8 (odh_dense_fill) into the bf16 operands' buffers, then the FP16
 //      (v_mfma_f32_32x32x16_f16) or INT8 (v_mfma_i32_32x32x32_i8) GEMM checked in registers against
-//      the closed form (odh_dense_probe_gemm_verify): autocast's default dtype and the W8A8 path.
+//      the closed form (odh_dense_probe_gemm_verify): autocast's default dtype and the W8A8 path;
+//   7. with --fp f32,f64 (the `amd.com/gpu-probe: "fp"` notebooks), after step 6 and before step 5,
+//      per format: the probe operands times odd constants as floats or doubles (odh_fp_fill) into
+//      the operands' buffers, which are then sized for them, and the FP32 (v_mfma_f32_32x32x2_f32)
+//      or FP64 (v_mfma_f64_16x16x4_f64) GEMM checked in registers against the closed form
+//      (odh_fp_probe_gemm_verify): torch's default dtype and NumPy's.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -81,7 +86,7 @@ struct Slot {
   float ms = 0;
 };
 
-// An optional GEMM step (--mx, --dtypes): per asked-for format, the probe operands re-encoded into
+// An optional GEMM step (--mx, --dtypes, --fp): per asked-for format, the probe operands re-encoded into
 // the bf16 operands' buffers and a fused check of that format's matrix-core instruction.
 struct Step {
   const char* word;  // the option (--word), the --inject-fault word and the verdict key
@@ -90,6 +95,7 @@ struct Step {
   // one format on one device, on the sweep's stream: fill, the fault if asked for, event, fused
   // verify, event, the counters copied back
   bool (*run)(Dev&, const Options&, int fmt, Slot&);
+  int (*tiles)(int fmt, int M, int N) = nullptr;  // workgroups of a format's kernel; null: the bf16 GEMM's
   std::vector<int> asked = {};  // the formats to check, in the order given
 
   const char* name(int fmt) const {
@@ -115,10 +121,11 @@ struct Step {
 
 bool mx_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run the other way round, --dtypes before --mx
-enum { STEP_MX, STEP_DTYPES, N_STEPS };
+// they run --dtypes, --fp, --mx
+enum { STEP_MX, STEP_DTYPES, STEP_FP, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -133,6 +140,7 @@ struct Options {
        {{"fp8", ODH_MX_FP8}, {"fp4", ODH_MX_FP4}, {"bf8", ODH_MX_BF8}, {"fp6", ODH_MX_FP6}, {"bf6", ODH_MX_BF6}},
        mx_run},
       {"dtypes", "GEMM", {{"f16", ODH_DT_F16}, {"i8", ODH_DT_I8}}, dt_run},  // tflops counts integer operations for i8
+      {"fp", "GEMM", {{"f32", ODH_FP_F32}, {"f64", ODH_FP_F64}}, fp_run, odh_fp_tiles},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -168,10 +176,17 @@ struct Dev {
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
-               "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--timeout-ms N] [--streams 0|1|2] "
-               "[--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes] [--quiet]\n",
+               "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--timeout-ms N] [--streams 0|1|2] "
+               "[--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] [--quiet]\n",
                argv0);
   return 64;
+}
+
+// the largest K at which every partial sum of the --fp operands, at most 6 K MUL_A MUL_B, is an
+// exact integer of the accumulator type: below 2^24 (f32) or 2^53 (f64)
+long long fp_max_k(int fmt) {
+  return fmt == ODH_FP_F64 ? ((1LL << 53) - 1) / (6LL * ODH_FP_F64_MUL_A * ODH_FP_F64_MUL_B)
+                           : ((1LL << 24) - 1) / (6LL * ODH_FP_F32_MUL_A * ODH_FP_F32_MUL_B);
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -224,12 +239,24 @@ bool parse(int argc, char** argv, Options& o) {
   if (!o.steps[STEP_MX].asked.empty() && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
   // --dtypes: the operands are the bf16 probe's (times constants for i8), so the K rules below
   // cover it: K % 64 == 0 is a whole number of f16 and of i8 stages, K % 35 != 0 a non-zero product
+  // --fp: the same operands times constants, floats or doubles: K % 64 == 0 is a whole number of their
+  // stages too, and every partial sum must stay an exact integer of the accumulator type
+  for (int fmt : o.steps[STEP_FP].asked)
+    if (o.K > fp_max_k(fmt)) return false;
   // a step's fault needs the step
   for (const Step& s : o.steps)
     if (o.fault == s.word && s.asked.empty()) return false;
   return o.M > 0 && o.N > 0 && o.K > 0 && o.M % 256 == 0 && o.N % 256 == 0 && o.K % 64 == 0 && o.K % 35 != 0 &&
          o.hbm_bytes >= (1u << 20) && o.timeout_ms > 0 && 2 * o.rccl_bytes <= o.hbm_bytes &&
          (o.fault != "rccl" || o.rccl_bytes > 0);
+}
+
+// bytes of an element of the A and Bt carve-outs: bf16's 2, or the widest --fp format's (its codes
+// are the element sizes)
+size_t operand_esize(const Options& o) {
+  size_t e = 2;
+  for (int fmt : o.steps[STEP_FP].asked) e = std::max(e, (size_t)fmt);
+  return e;
 }
 
 void emit(const Options& o, const std::string& json) {
@@ -286,11 +313,12 @@ size_t align_up(size_t x) { return (x + 4095) & ~(size_t)4095; }
 // then the streams and events.  Host-side set-up time is what the notebook pod waits for.
 bool setup_alloc(Dev& d, const Options& o) {
   HIP_TRY(hipSetDevice(d.index));
-  const size_t na = align_up((size_t)o.M * o.K * 2), nb = align_up((size_t)o.N * o.K * 2);
+  const size_t esz = operand_esize(o);
+  const size_t na = align_up((size_t)o.M * o.K * esz), nb = align_up((size_t)o.N * o.K * esz);
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
   // every optional step adds a counter block per format behind the first; --mx also the scales of both
-  // operands and the table, --dtypes nothing else: its operands are no larger
+  // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands
   size_t nslots = 0;
   for (const Step& s : o.steps) nslots += s.asked.size();
   const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
@@ -427,6 +455,27 @@ bool dt_run(Dev& d, const Options& o, int fmt, Slot& s) {
   }
   HIP_TRY(hipEventRecord(s.e0, d.sh));
   HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a format of --fp, after --dtypes and before --mx: the operands times odd constants as floats or
+// doubles into the operands' buffers (sized for the widest asked-for format), then the fused check
+bool fp_run(Dev& d, const Options& o, int fmt, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_fp_fill(fmt, d.a, d.bt, o.M, o.N, o.K, d.sh));
+  if (o.fault == "fp") {
+    // A[0][0] becomes +MUL_A (the fill has -2 MUL_A): row 0 of C is wrong wherever Bt[j][0] != 0
+    static const float one32 = ODH_FP_F32_MUL_A;
+    static const double one64 = ODH_FP_F64_MUL_A;
+    if (fmt == ODH_FP_F64)
+      HIP_TRY(hipMemcpyAsync(d.a, &one64, sizeof one64, hipMemcpyHostToDevice, d.sh));
+    else
+      HIP_TRY(hipMemcpyAsync(d.a, &one32, sizeof one32, hipMemcpyHostToDevice, d.sh));
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_fp_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
@@ -694,11 +743,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, then --mx: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, then --mx: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_MX}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_MX}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -810,10 +859,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[96] = "";
+  char step_timing[128] = "";
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     for (size_t f = 0; f < s.asked.size(); ++f) {
+      const int ftiles = s.tiles ? s.tiles(s.asked[f], o.M, o.N) : tiles;
       uint64_t errs = 0;
       float slowest = 0;
       bool fok = true;
@@ -829,12 +879,12 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
         const uint32_t e = (uint32_t)h[ODH_SLOT_GEMM_ERR];
         errs += e;
         slowest = slot.ms > slowest ? slot.ms : slowest;
-        if (e == 0 && blocks == tiles) continue;
+        if (e == 0 && blocks == ftiles) continue;
         fok = false;
         if (first_err.empty()) {
           char b[200];
           std::snprintf(b, sizeof b, "GPU %d: %s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index,
-                        s.name(s.asked[f]), e, s.what, where.empty() ? "-" : where.c_str(), blocks, tiles);
+                        s.name(s.asked[f]), e, s.what, where.empty() ? "-" : where.c_str(), blocks, ftiles);
           first_err = b;
         }
       }

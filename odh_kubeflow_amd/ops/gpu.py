@@ -21,6 +21,9 @@
 * :func:`dense_fill`, :func:`dense_gemm`, :func:`dense_probe` — the FP16 and INT8 paths
   (``v_mfma_f32_32x32x16_f16``, ``v_mfma_i32_32x32x32_i8``) on float16 / int8 tensors: the same
   check against the bf16 probe's 5 × 7 closed form (``odh-gpu-probe --dtypes``).
+* :func:`fp_fill`, :func:`fp_gemm`, :func:`fp_probe` — the FP32 and FP64 paths
+  (``v_mfma_f32_32x32x2_f32``, ``v_mfma_f64_16x16x4_f64``) on float32 / float64 tensors: the same
+  check against that closed form times odd constants (``odh-gpu-probe --fp``).
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
@@ -80,6 +83,14 @@ ODH_DT_I8 = 2  # int8, int32 accumulation
 ODH_DT_I8_MUL_A = 25  # the i8 probe operands are these odd multiples of the bf16 probe's A ...
 ODH_DT_I8_MUL_B = 41  # ... and Bt: the expected product is 1025 × the bf16 probe's
 DENSE_FORMATS = {"f16": ODH_DT_F16, "i8": ODH_DT_I8}
+# operand formats of the FP32 / FP64 kernels (csrc/gpu_probe_fp.h): the codes are the element sizes
+ODH_FP_F32 = 4  # float, fp32 accumulation
+ODH_FP_F64 = 8  # double, fp64 accumulation
+ODH_FP_F32_MUL_A = 25  # the f32 probe operands are the i8 probe's multiples of the bf16 probe's A ...
+ODH_FP_F32_MUL_B = 41  # ... and Bt: 1025 × the bf16 probe's product
+ODH_FP_F64_MUL_A = 1048573  # the f64 probe operands: odd 20-bit multiples ...
+ODH_FP_F64_MUL_B = 1048575  # ... whose products toggle 41 mantissa bits
+FP_FORMATS = {"f32": ODH_FP_F32, "f64": ODH_FP_F64}
 
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -116,6 +127,11 @@ SIGNATURES = {
     "odh_dense_fill": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
     "odh_dense_gemm": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_dense_probe_gemm_verify": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # FP32 / FP64 (csrc/gpu_probe_fp.h)
+    "odh_fp_tiles": (_i, [_i, _i, _i]),
+    "odh_fp_fill": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_fp_gemm": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_fp_probe_gemm_verify": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -284,7 +300,7 @@ def mx_zero_classes(k: int) -> int:
 
 
 def _same_gpu_2d(family: str, what: str, dtype, dtype_error: str, *ts) -> None:
-    """What every MX and dense entry point asks of its tensors before launch: ``dtype``, 2-D, one
+    """What every MX, dense and fp entry point asks of its tensors before launch: ``dtype``, 2-D, one
     GPU, contiguous."""
     if any(t.dtype != dtype for t in ts):
         raise TypeError(dtype_error)
@@ -296,14 +312,17 @@ def _same_gpu_2d(family: str, what: str, dtype, dtype_error: str, *ts) -> None:
         raise ValueError(f"{what} must be contiguous")
 
 
-def _fused_check(dev, m: int, n: int, k: int, launch) -> dict:
+def _fused_check(dev, m: int, n: int, k: int, launch, tiles: Optional[int] = None) -> dict:
     """A fused check on a fresh counter block, and its report.  ``launch(tile_xcd, counters, stream)``
-    is the one kernel launch; its time is taken with events around it."""
+    is the one kernel launch; its time is taken with events around it.  ``tiles`` is the kernel's
+    workgroup count (256² output tiles unless given)."""
     import torch
 
+    if tiles is None:
+        tiles = (m // 256) * (n // 256)
     with torch.cuda.device(dev):
         counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
-        tile_xcd = torch.full(((m // 256) * (n // 256),), -1, dtype=torch.int32, device=dev)
+        tile_xcd = torch.full((tiles,), -1, dtype=torch.int32, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         _check(launch(tile_xcd.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
@@ -482,6 +501,107 @@ def dense_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[
         bt = torch.empty((n, k), dtype=dtype, device=dev)
         dense_fill(code, a, bt)
         return dense_verify(code, a, bt)
+
+
+def _fp_format(fmt) -> int:
+    code = FP_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in FP_FORMATS.values():
+        raise ValueError(f"fp format must be one of {sorted(FP_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def fp_shape_ok(fmt, m: int, n: int, k: int) -> bool:
+    """256-row and 256-column multiples, and K in stages of 64 bytes per row: 16 floats or 8 doubles."""
+    bk = 64 // _fp_format(fmt)
+    return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
+
+
+def fp_k_exact(fmt, k: int) -> bool:
+    """Whether every partial sum of the fp probe operands, at most ``6 K MUL_A MUL_B``, is an exact
+    integer of the accumulator type: below 2^24 (f32, K <= 2728) or 2^53 (f64, K <= 1365)."""
+    if _fp_format(fmt) == ODH_FP_F64:
+        return 6 * k * ODH_FP_F64_MUL_A * ODH_FP_F64_MUL_B < 2 ** 53
+    return 6 * k * ODH_FP_F32_MUL_A * ODH_FP_F32_MUL_B < 2 ** 24
+
+
+def fp_tiles(fmt, m: int, n: int) -> int:
+    """Workgroups the fp kernels launch: 256×256 output tiles for f32, 256×128 for f64."""
+    return load_library().odh_fp_tiles(_fp_format(fmt), m, n)
+
+
+def _fp_operands(fmt, a, bt, probe: bool = False):
+    """Checks of the fp entry points, before launch: float32 (f32) or float64 (f64), one GPU,
+    contiguous, 16-byte aligned, A ``[M, K]`` and Bt ``[N, K]``; ``probe``: a K at which the probe
+    operands are exact.
+    Returns the format code and M, N, K."""
+    import torch
+
+    code = _fp_format(fmt)
+    name, want = ("f64", torch.float64) if code == ODH_FP_F64 else ("f32", torch.float32)
+    _same_gpu_2d("fp", "operands", want, f"{name} operands are {want}", a, bt)
+    m, k = a.shape
+    n = bt.shape[0]
+    if bt.shape[1] != k or not fp_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {64 // code}; "
+                         f"got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    if a.data_ptr() % 16 or bt.data_ptr() % 16:
+        raise ValueError("operands must be 16-byte aligned")
+    if probe and not fp_k_exact(code, k):
+        raise ValueError(f"the {name} probe operands are not exact at K = {k}")
+    return code, m, n, k
+
+
+def fp_fill(fmt, a, bt) -> None:
+    """The probe operands for ``fmt`` written into the given tensors: the bf16 probe's families
+    times ``ODH_FP_F32_MUL_A`` / ``_B`` as floats (``"f32"``) or ``ODH_FP_F64_MUL_A`` / ``_B`` as
+    doubles (``"f64"``)."""
+    code, m, n, k = _fp_operands(fmt, a, bt, probe=True)
+    _check(load_library().odh_fp_fill(code, a.data_ptr(), bt.data_ptr(), m, n, k, _stream_ptr(a.device)))
+
+
+def fp_gemm(fmt, a, bt, out=None):
+    """``C[M,N] = A[M,K] · Bt[N,K]ᵀ`` on the FP32 (``v_mfma_f32_32x32x2_f32``) or FP64
+    (``v_mfma_f64_16x16x4_f64``) matrix cores, out in the operands' type."""
+    import torch
+
+    code, m, n, k = _fp_operands(fmt, a, bt)
+    want = a.dtype
+    if out is None:
+        out = torch.empty((m, n), dtype=want, device=a.device)
+    elif tuple(out.shape) != (m, n) or out.dtype != want or not out.is_contiguous() or out.device != a.device:
+        raise ValueError(f"out must be a contiguous {want} [M,N] tensor on the operands' GPU")
+    _check(load_library().odh_fp_gemm(code, a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k,
+                                      _stream_ptr(a.device)))
+    return out
+
+
+def fp_verify(fmt, a, bt) -> dict:
+    """The fused check of the given operands against the closed form on a fresh counter block;
+    the kernel's time is taken with events around its one launch.  The dict of :func:`mx_verify`."""
+    code, m, n, k = _fp_operands(fmt, a, bt, probe=True)
+
+    def launch(tile_xcd, counters, stream):
+        return load_library().odh_fp_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), m, n, k, tile_xcd,
+                                                       counters, stream)
+
+    return _fused_check(a.device, m, n, k, launch, tiles=fp_tiles(code, m, n))
+
+
+def fp_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
+    """One FP32 / FP64 probe of a GPU: fill, then the GEMM with the check fused into its
+    epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
+    import torch
+
+    code = _fp_format(fmt)
+    if not fp_shape_ok(code, m, n, k) or not fp_k_exact(code, k):
+        raise ValueError("fp probe shape must be tile aligned, with a K at which the operands are exact")
+    dev = torch.device("cuda", device)
+    dtype = torch.float64 if code == ODH_FP_F64 else torch.float32
+    with torch.cuda.device(dev):
+        a = torch.empty((m, k), dtype=dtype, device=dev)
+        bt = torch.empty((n, k), dtype=dtype, device=dev)
+        fp_fill(code, a, bt)
+        return fp_verify(code, a, bt)
 
 
 class GpuProbe:
