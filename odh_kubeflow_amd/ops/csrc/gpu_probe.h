@@ -45,6 +45,13 @@ enum {
   ODH_FP_F32_MUL_B = 41,  // ... and Bt: 1025 × the bf16 probe's product, exact in fp32 while 6150 K < 2^24
   ODH_FP_F64_MUL_A = 1048573,  // the f64 probe operands: odd 20-bit multiples ...
   ODH_FP_F64_MUL_B = 1048575,  // ... whose products toggle 41 mantissa bits; exact in fp64 at K <= 1365
+  // operand formats of the 2:4 structured-sparsity kernels (gpu_probe_sparse.h)
+  ODH_SP_BF16 = 0,  // bfloat16, 32x32x32, fp32 accumulation
+  ODH_SP_F16 = 1,   // IEEE half, 32x32x32, fp32 accumulation
+  ODH_SP_I8 = 2,    // int8, 32x32x64, int32 accumulation
+  ODH_SP_FP8 = 3,   // OCP e4m3fn on both operands, 32x32x64, fp32 accumulation
+  ODH_SP_BF8 = 4,   // OCP e5m2 on both operands, 32x32x64, fp32 accumulation
+  ODH_SP_CLASSES = 210,  // ints in the table of expected values: (i mod 30, j mod 7)
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -114,6 +121,20 @@ int odh_fp_fill(int fmt, void* A, void* Bt, int M, int N, int K, hipStream_t str
 int odh_fp_gemm(int fmt, const void* A, const void* Bt, void* C, int M, int N, int K, hipStream_t stream);
 int odh_fp_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int N, int K, int* tile_xcd,
                              int* counters, hipStream_t stream);
+// 2:4 structured sparsity (fmt: ODH_SP_*): C = A · Btᵀ with two of every four consecutive elements of an A row
+// kept.  Ac [M][K/2]: the kept elements, 2g and 2g+1 those of group g (dense columns 4g … 4g+3); meta [M][K/8]
+// bytes: group g of a row is the nibble at bits [4g, 4g+4) of the row, little endian, p0 | p1 << 2 = the dense
+// positions of its two kept elements, p0 < p1 (a nibble with p0 >= p1 is unspecified); Bt [N][K] dense, in A's
+// element type: bf16, half, int8 or one-byte e4m3fn / e5m2 codes; C [M][N] fp32, int32 for i8.  Ac and Bt are
+// 16-byte aligned, meta 4-byte aligned; M and N multiples of 256, K of 64 (bf16, f16) or 128 (i8, fp8, bf8);
+// table: ODH_SP_CLASSES ints, the expected sums of the probe operands; counters as for the dense kernels.
+// odh_sparse_fill and odh_sparse_probe_gemm_verify refuse a K at which a class expects 0
+int odh_sparse_zero_classes(int K);  // host only: classes expecting 0 at this K (-1: K not a positive multiple of 64)
+int odh_sparse_fill(int fmt, void* Ac, void* meta, void* Bt, int* table, int M, int N, int K, hipStream_t stream);
+int odh_sparse_gemm(int fmt, const void* Ac, const void* meta, const void* Bt, void* C, int M, int N, int K,
+                    hipStream_t stream);
+int odh_sparse_probe_gemm_verify(int fmt, const void* Ac, const void* meta, const void* Bt, const int* table, int M,
+                                 int N, int K, int* tile_xcd, int* counters, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

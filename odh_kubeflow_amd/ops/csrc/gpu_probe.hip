@@ -39,6 +39,10 @@
 //  * odh_fp_fill / odh_fp_gemm / odh_fp_probe_gemm_verify — the same exact check on the FP32 and
 //    FP64 paths (v_mfma_f32_32x32x2_f32, v_mfma_f64_16x16x4_f64; gpu_probe_fp.h): the ring again, with
 //    floats or doubles in its 64-byte stage rows and a 256×128 tile for f64 (odh_fp_tiles).
+//  * odh_sparse_fill / odh_sparse_gemm / odh_sparse_probe_gemm_verify — the same exact check on the 2:4
+//    structured-sparsity path (v_smfmac_*: bf16, f16, i8, fp8, bf8; gpu_probe_sparse.h): compressed A,
+//    metadata and dense Bt on a three-slot ring, against a 30 × 7 table, and odh_sparse_zero_classes, the
+//    host-side guard against a K at which that check is blind.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -47,6 +51,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "gpu_probe.h"
 
@@ -586,6 +592,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm256d_kernel(
 #include "gpu_probe_mx.h"  // the block-scaled kernels (FP8, BF8, FP6, BF6, MXFP4), on the tile helpers above
 #include "gpu_probe_dense.h"  // the FP16 / INT8 kernels, on the same helpers and the ring above
 #include "gpu_probe_fp.h"  // the FP32 / FP64 kernels, on the same helpers and the ring's constants
+#include "gpu_probe_sparse.h"  // the 2:4 structured-sparsity kernels, on the same helpers and a ring of their own
 
 __device__ __forceinline__ uint16_t small_int_bf16(int v) {
   // exact for |v| < 256: take the high half of the f32 bit pattern
@@ -1250,6 +1257,51 @@ int odh_fp_probe_gemm_verify(int fmt, const void* A, const void* Bt, int M, int 
   unsigned* c = (unsigned*)counters;
   fp_launch_gemm<true>(fmt, fp_tiles(fmt, M, N), stream, (const uint4*)A, (const uint4*)Bt, (void*)nullptr, N, K,
                        tile_xcd, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ 2:4 structured sparsity (gpu_probe_sparse.h)
+
+// host only (no HIP call): how many of the 210 (i mod 30, j mod 7) classes expect 0 at this K, where
+// the check cannot tell a right product from an all-zero one; -1 for a K that is not a positive
+// multiple of 64
+int odh_sparse_zero_classes(int K) { return K <= 0 || K % 64 ? -1 : sparse_zero_classes(K); }
+
+// the probe operands pruned 2:4 and encoded for fmt, their metadata, and the 30 × 7 table of
+// expected sums
+int odh_sparse_fill(int fmt, void* Ac, void* meta, void* Bt, int* table, int M, int N, int K, hipStream_t stream) {
+  if (!sparse_ok(fmt, M, N, K) || !sparse_aligned(Ac, meta, Bt) || !table || sparse_zero_classes(K) != 0)
+    return (int)hipErrorInvalidValue;
+  const size_t n = (size_t)M * (size_t)(K / 8) + (size_t)N * (size_t)K;
+  sparse_fill_kernel<<<grid_for(n, 256), 256, 0, stream>>>(fmt, Ac, (uint8_t*)meta, Bt, M, N, K);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  sparse_table_kernel<<<ODH_SP_CLASSES, 64, 0, stream>>>(table, K);
+  return (int)hipGetLastError();
+}
+
+// C[M][N] = A · Btᵀ for any compressed A with valid metadata and any Bt: fp32, or int32 out of int8
+int odh_sparse_gemm(int fmt, const void* Ac, const void* meta, const void* Bt, void* C, int M, int N, int K,
+                    hipStream_t stream) {
+  if (!sparse_ok(fmt, M, N, K) || !sparse_aligned(Ac, meta, Bt) || !C || ((uintptr_t)C & 3))
+    return (int)hipErrorInvalidValue;
+  sparse_launch_gemm<false>(fmt, gemm256_tiles(M, N), stream, (const uint4*)Ac, (const uint32_t*)meta,
+                            (const uint4*)Bt, C, (const int*)nullptr, N, K, (int*)nullptr, (int*)nullptr,
+                            (unsigned*)nullptr, (unsigned*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// the same tiles on odh_sparse_fill's operands with the check against its table fused into the
+// epilogue; counters is a counter block of this format's own
+int odh_sparse_probe_gemm_verify(int fmt, const void* Ac, const void* meta, const void* Bt, const int* table, int M,
+                                 int N, int K, int* tile_xcd, int* counters, hipStream_t stream) {
+  if (!sparse_ok(fmt, M, N, K) || !sparse_aligned(Ac, meta, Bt) || !table || !counters ||
+      sparse_zero_classes(K) != 0)
+    return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  sparse_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)Ac, (const uint32_t*)meta,
+                           (const uint4*)Bt, (void*)nullptr, table, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+                           c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

@@ -35,7 +35,12 @@
 //      per format: the probe operands times odd constants as floats or doubles (odh_fp_fill) into
 //      the operands' buffers, which are then sized for them, and the FP32 (v_mfma_f32_32x32x2_f32)
 //      or FP64 (v_mfma_f64_16x16x4_f64) GEMM checked in registers against the closed form
-//      (odh_fp_probe_gemm_verify): torch's default dtype and NumPy's.
+//      (odh_fp_probe_gemm_verify): torch's default dtype and NumPy's;
+//   8. with --sparse bf16,f16,i8,fp8,bf8 (the `amd.com/gpu-probe: "sparse"` notebooks), after step 7 and
+//      before step 5, per format: the probe's A pruned 2:4 and compressed, its metadata and the dense Bt
+//      (odh_sparse_fill) into the operands' buffers, and the structured-sparsity GEMM (v_smfmac_*) checked
+//      in registers against a 30 × 7 table (odh_sparse_probe_gemm_verify): the index operand and the
+//      selection multiplexers a pruned model runs on, which no dense instruction touches.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -86,7 +91,7 @@ struct Slot {
   float ms = 0;
 };
 
-// An optional GEMM step (--mx, --dtypes, --fp): per asked-for format, the probe operands re-encoded into
+// An optional GEMM step (--mx, --dtypes, --fp, --sparse): per asked-for format, the probe operands re-encoded into
 // the bf16 operands' buffers and a fused check of that format's matrix-core instruction.
 struct Step {
   const char* word;  // the option (--word), the --inject-fault word and the verdict key
@@ -122,10 +127,11 @@ struct Step {
 bool mx_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --mx
-enum { STEP_MX, STEP_DTYPES, STEP_FP, N_STEPS };
+// they run --dtypes, --fp, --sparse, --mx
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -141,6 +147,9 @@ struct Options {
        mx_run},
       {"dtypes", "GEMM", {{"f16", ODH_DT_F16}, {"i8", ODH_DT_I8}}, dt_run},  // tflops counts integer operations for i8
       {"fp", "GEMM", {{"f32", ODH_FP_F32}, {"f64", ODH_FP_F64}}, fp_run, odh_fp_tiles},
+      {"sparse", "sparse GEMM",  // tflops counts the dense-equivalent 2 M N K
+       {{"bf16", ODH_SP_BF16}, {"f16", ODH_SP_F16}, {"i8", ODH_SP_I8}, {"fp8", ODH_SP_FP8}, {"bf8", ODH_SP_BF8}},
+       sp_run},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -169,6 +178,9 @@ struct Dev {
   // --mx: scales and table behind the counters
   void *mx_sa = nullptr, *mx_sbt = nullptr;
   float* mx_table = nullptr;
+  // --sparse: metadata and table behind those
+  void* sp_meta = nullptr;
+  int* sp_table = nullptr;
   std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
   std::string error;
 };
@@ -176,8 +188,9 @@ struct Dev {
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
-               "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--timeout-ms N] [--streams 0|1|2] "
-               "[--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] [--quiet]\n",
+               "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--sparse bf16,f16,i8,fp8,bf8] "
+               "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
+               "[--inject-fault sparse] [--quiet]\n",
                argv0);
   return 64;
 }
@@ -243,6 +256,11 @@ bool parse(int argc, char** argv, Options& o) {
   // stages too, and every partial sum must stay an exact integer of the accumulator type
   for (int fmt : o.steps[STEP_FP].asked)
     if (o.K > fp_max_k(fmt)) return false;
+  // --sparse: 64 is a stage of its 16-bit formats, 128 of its 8-bit ones, and none of the 210 classes of the
+  // pruned operands may expect 0 (odh_sparse_zero_classes: host arithmetic, before any HIP call)
+  if (!o.steps[STEP_SPARSE].asked.empty() && odh_sparse_zero_classes(o.K) != 0) return false;
+  for (int fmt : o.steps[STEP_SPARSE].asked)
+    if (fmt != ODH_SP_BF16 && fmt != ODH_SP_F16 && o.K % 128 != 0) return false;
   // a step's fault needs the step
   for (const Step& s : o.steps)
     if (o.fault == s.word && s.asked.empty()) return false;
@@ -318,13 +336,17 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
   // every optional step adds a counter block per format behind the first; --mx also the scales of both
-  // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands
+  // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
+  // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands)
   size_t nslots = 0;
   for (const Step& s : o.steps) nslots += s.asked.size();
   const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab));
+  const bool sparse = !o.steps[STEP_SPARSE].asked.empty();
+  const size_t nmeta = sparse ? align_up((size_t)o.M * (o.K / 8)) : 0;
+  const size_t nsptab = sparse ? align_up(sizeof(int) * ODH_SP_CLASSES) : 0;
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -336,6 +358,10 @@ bool setup_alloc(Dev& d, const Options& o) {
     d.mx_sa = p + na + nb + nh + nt + nc;
     d.mx_sbt = p + na + nb + nh + nt + nc + nsa;
     d.mx_table = (float*)(p + na + nb + nh + nt + nc + nsa + nsb);
+  }
+  if (sparse) {
+    d.sp_meta = p + na + nb + nh + nt + nc + nsa + nsb + ntab;
+    d.sp_table = (int*)(p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta);
   }
   int* block = d.counters;
   for (int s = 0; s < N_STEPS; ++s) {
@@ -476,6 +502,25 @@ bool fp_run(Dev& d, const Options& o, int fmt, Slot& s) {
   }
   HIP_TRY(hipEventRecord(s.e0, d.sh));
   HIP_TRY(odh_fp_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a format of --sparse, after --fp and before --mx: the pruned A compressed, its metadata and the dense Bt
+// (no larger than the bf16 operands) with the table, then the fused check
+bool sp_run(Dev& d, const Options& o, int fmt, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_sparse_fill(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, d.sh));
+  if (o.fault == "sparse") {
+    // the nibble of row 0, group 0 becomes the pair (0,1) (the fill has (0,3); byte 0 is 0xEC, group 1
+    // in its high nibble): the kept A[0][3] = -1 meets Bt[j][1] instead of Bt[j][3], which differ for
+    // every j, so row 0 of C is wrong in every column
+    HIP_TRY(hipMemsetAsync(d.sp_meta, 0xE4, 1, d.sh));
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_sparse_probe_gemm_verify(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, nullptr, s.counters,
+                                       d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
@@ -743,11 +788,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, then --mx: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, --sparse, then --mx: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_MX}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -859,7 +904,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[128] = "";
+  char step_timing[192] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     for (size_t f = 0; f < s.asked.size(); ++f) {

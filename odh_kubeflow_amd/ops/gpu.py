@@ -24,6 +24,10 @@
 * :func:`fp_fill`, :func:`fp_gemm`, :func:`fp_probe` — the FP32 and FP64 paths
   (``v_mfma_f32_32x32x2_f32``, ``v_mfma_f64_16x16x4_f64``) on float32 / float64 tensors: the same
   check against that closed form times odd constants (``odh-gpu-probe --fp``).
+* :func:`sparse_fill`, :func:`sparse_gemm`, :func:`sparse_probe` — the 2:4 structured-sparsity path
+  (``v_smfmac_*`` on bf16, f16, int8, fp8 and bf8) on a compressed A, its metadata and a dense Bt: the
+  same check against a 30 × 7 table (``odh-gpu-probe --sparse``); :func:`sparse_compress` and
+  :func:`sparse_decompress` turn a dense tensor into that layout and back, in plain torch.
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
@@ -91,6 +95,15 @@ ODH_FP_F32_MUL_B = 41  # ... and Bt: 1025 × the bf16 probe's product
 ODH_FP_F64_MUL_A = 1048573  # the f64 probe operands: odd 20-bit multiples ...
 ODH_FP_F64_MUL_B = 1048575  # ... whose products toggle 41 mantissa bits
 FP_FORMATS = {"f32": ODH_FP_F32, "f64": ODH_FP_F64}
+# operand formats of the 2:4 structured-sparsity kernels (csrc/gpu_probe_sparse.h)
+ODH_SP_BF16 = 0  # bfloat16, fp32 accumulation
+ODH_SP_F16 = 1  # IEEE half, fp32 accumulation
+ODH_SP_I8 = 2  # int8, int32 accumulation
+ODH_SP_FP8 = 3  # OCP e4m3fn on both operands, fp32 accumulation
+ODH_SP_BF8 = 4  # OCP e5m2 on both operands, fp32 accumulation
+ODH_SP_CLASSES = 210  # ints in the table of expected values
+SPARSE_FORMATS = {"bf16": ODH_SP_BF16, "f16": ODH_SP_F16, "i8": ODH_SP_I8, "fp8": ODH_SP_FP8, "bf8": ODH_SP_BF8}
+SPARSE_TABLE = (30, 7)  # expected sums of the sparse probe operands, by (i mod 30, j mod 7)
 
 _vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -132,6 +145,11 @@ SIGNATURES = {
     "odh_fp_fill": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
     "odh_fp_gemm": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_fp_probe_gemm_verify": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # 2:4 structured sparsity (csrc/gpu_probe_sparse.h)
+    "odh_sparse_zero_classes": (_i, [_i]),
+    "odh_sparse_fill": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_sparse_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_sparse_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -300,7 +318,7 @@ def mx_zero_classes(k: int) -> int:
 
 
 def _same_gpu_2d(family: str, what: str, dtype, dtype_error: str, *ts) -> None:
-    """What every MX, dense and fp entry point asks of its tensors before launch: ``dtype``, 2-D, one
+    """What every MX, dense, fp and sparse entry point asks of its tensors before launch: ``dtype``, 2-D, one
     GPU, contiguous."""
     if any(t.dtype != dtype for t in ts):
         raise TypeError(dtype_error)
@@ -602,6 +620,189 @@ def fp_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1],
         bt = torch.empty((n, k), dtype=dtype, device=dev)
         fp_fill(code, a, bt)
         return fp_verify(code, a, bt)
+
+
+def _sparse_format(fmt) -> int:
+    code = SPARSE_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in SPARSE_FORMATS.values():
+        raise ValueError(f"sparse format must be one of {sorted(SPARSE_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def _sparse_stage(code: int) -> int:
+    """Dense elements of a row per stage: 128 bytes of a Bt row."""
+    return 64 if code in (ODH_SP_BF16, ODH_SP_F16) else 128
+
+
+def _sparse_dtype(code: int):
+    import torch
+
+    return {ODH_SP_BF16: torch.bfloat16, ODH_SP_F16: torch.float16, ODH_SP_I8: torch.int8,
+            ODH_SP_FP8: torch.float8_e4m3fn, ODH_SP_BF8: torch.float8_e5m2}[code]
+
+
+def sparse_shape_ok(fmt, m: int, n: int, k: int) -> bool:
+    """256² output tiles, and K (the dense one) in whole stages: 64 bf16 or f16 elements, 128 i8, fp8 or bf8."""
+    bk = _sparse_stage(_sparse_format(fmt))
+    return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
+
+
+def sparse_zero_classes(k: int) -> int:
+    """How many of the 210 ``(i mod 30, j mod 7)`` classes of the sparse probe operands expect 0 at
+    this K (-1: K is no positive multiple of 64).  Host arithmetic only."""
+    return load_library().odh_sparse_zero_classes(k)
+
+
+def _raw_view(t):
+    """An integer view of a tensor's elements (gather and scatter take every integer dtype)."""
+    import torch
+
+    if not t.dtype.is_floating_point:
+        return t
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def sparse_compress(a, prune: bool = False):
+    """A dense ``[M, K]`` tensor (CPU or GPU, K a multiple of 8) with at most two non-zeros in every
+    group of four consecutive elements of a row, as ``(ac, meta)`` in the layout of :func:`sparse_gemm`:
+    ``ac`` is ``[M, K/2]`` in ``a``'s dtype, elements ``2g`` and ``2g + 1`` the kept ones of group ``g``;
+    ``meta`` is ``[M, K/8]`` uint8, group ``g`` the nibble at bits ``[4g, 4g + 4)`` of the row,
+    ``p0 | p1 << 2`` with ``p0 < p1`` the kept positions.  A group with more than two non-zeros raises
+    ``ValueError`` (naming row and group) unless ``prune``, which keeps the two largest magnitudes
+    of each group, ties to the lower position.  A group with fewer than two non-zeros keeps them
+    and the lowest other positions, so every nibble is valid."""
+    import torch
+
+    if a.dim() != 2 or a.shape[1] % 8:
+        raise ValueError(f"a must be [M, K] with K a multiple of 8; got {tuple(a.shape)}")
+    m, k = a.shape
+    val = a.double() if a.dtype.is_floating_point else a.long()
+    groups = val.reshape(m, k // 4, 4)
+    if prune:
+        key = groups.abs()
+    else:
+        key = (groups != 0).to(torch.int64)
+        over = (key.sum(-1) > 2).nonzero()
+        if over.numel():
+            r, g = over[0].tolist()
+            raise ValueError(f"row {r}, group {g} (columns {4 * g} … {4 * g + 3}) has more than two non-zeros")
+    # the two largest keys of a group, ties to the lower position, in ascending position
+    order = torch.sort(key, dim=-1, descending=True, stable=True).indices[..., :2]
+    pos = torch.sort(order, dim=-1).values
+    ac = torch.gather(_raw_view(a.contiguous()).reshape(m, k // 4, 4), -1, pos).reshape(m, k // 2).view(a.dtype)
+    nib = (pos[..., 0] | (pos[..., 1] << 2)).reshape(m, k // 8, 2)
+    meta = (nib[..., 0] | (nib[..., 1] << 4)).to(torch.uint8)
+    return ac.contiguous(), meta.contiguous()
+
+
+def sparse_decompress(ac, meta):
+    """The dense ``[M, K]`` tensor of a compressed ``ac`` ``[M, K/2]`` and its ``meta`` ``[M, K/8]``
+    (nibbles with ``p0 < p1``): the inverse of :func:`sparse_compress`."""
+    import torch
+
+    if ac.dim() != 2 or meta.dim() != 2 or meta.dtype != torch.uint8 or ac.shape[0] != meta.shape[0] \
+            or ac.shape[1] != 4 * meta.shape[1]:
+        raise ValueError(f"ac must be [M, K/2] and meta [M, K/8] uint8; got {tuple(ac.shape)} {tuple(meta.shape)}")
+    m, g = ac.shape[0], ac.shape[1] // 2
+    nib = torch.stack((meta & 15, meta >> 4), dim=-1).reshape(m, g).long()
+    pos = torch.stack((nib & 3, nib >> 2), dim=-1)
+    raw = _raw_view(ac.contiguous())
+    out = torch.zeros((m, g, 4), dtype=raw.dtype, device=ac.device)
+    out.scatter_(-1, pos, raw.reshape(m, g, 2))
+    return out.reshape(m, 4 * g).view(ac.dtype)
+
+
+def _sparse_operands(fmt, ac, meta, bt, probe: bool = False):
+    """Checks of the sparse entry points, before launch: ``ac`` ``[M, K/2]`` and ``bt`` ``[N, K]`` in the
+    format's dtype (bfloat16, float16, int8, float8_e4m3fn, float8_e5m2), ``meta`` ``[M, K/8]`` uint8,
+    one GPU, contiguous, aligned; ``probe``: a K at which no class of the probe operands expects 0.
+    Returns the format code and M, N, K."""
+    import torch
+
+    code = _sparse_format(fmt)
+    want = _sparse_dtype(code)
+    name = next(n for n, c in SPARSE_FORMATS.items() if c == code)
+    _same_gpu_2d("sparse", "operands", want, f"{name} operands are {want}", ac, bt)
+    _same_gpu_2d("sparse", "operands and metadata", torch.uint8, "sparse metadata is uint8", meta)
+    if meta.device != ac.device:
+        raise ValueError("operands and metadata must live on the same GPU")
+    m, n, k = ac.shape[0], bt.shape[0], bt.shape[1]
+    if 2 * ac.shape[1] != k or tuple(meta.shape) != (m, k // 8) or not sparse_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {_sparse_stage(code)}, Ac [M,K/2], meta [M,K/8]; "
+                         f"got Ac{tuple(ac.shape)} meta{tuple(meta.shape)} Bt{tuple(bt.shape)}")
+    if ac.data_ptr() % 16 or bt.data_ptr() % 16 or meta.data_ptr() % 4:
+        raise ValueError("operands must be 16-byte aligned and metadata 4-byte aligned")
+    if probe and sparse_zero_classes(k) != 0:
+        raise ValueError(f"a class of the sparse probe operands expects 0 at K = {k}")
+    return code, m, n, k
+
+
+def _sparse_table(table, dev) -> None:
+    import torch
+
+    if (table.dtype != torch.int32 or tuple(table.shape) != SPARSE_TABLE or not table.is_contiguous()
+            or table.device != dev):
+        raise ValueError("table must be a contiguous int32 [30,7] tensor on the operands' GPU")
+
+
+def sparse_fill(fmt, ac, meta, bt, table) -> None:
+    """The sparse probe operands for ``fmt`` written into the given tensors: the bf16 probe's A pruned
+    2:4 by a selector that uses all six position pairs, compressed, with its metadata; the dense Bt;
+    and the 30 × 7 int32 table of expected sums (of the small integers: ``"i8"`` operands are
+    those times ``ODH_DT_I8_MUL_A`` / ``ODH_DT_I8_MUL_B``, and the check scales the table)."""
+    code, m, n, k = _sparse_operands(fmt, ac, meta, bt, probe=True)
+    _sparse_table(table, ac.device)
+    _check(load_library().odh_sparse_fill(code, ac.data_ptr(), meta.data_ptr(), bt.data_ptr(), table.data_ptr(),
+                                          m, n, k, _stream_ptr(ac.device)))
+
+
+def sparse_gemm(fmt, ac, meta, bt, out=None):
+    """``C[M,N] = A[M,K] · Bt[N,K]ᵀ`` for a 2:4-sparse A given as :func:`sparse_compress` returns it, on
+    the structured-sparsity matrix cores (``v_smfmac_*``): fp32 out, int32 for ``"i8"``."""
+    import torch
+
+    code, m, n, k = _sparse_operands(fmt, ac, meta, bt)
+    want = torch.int32 if code == ODH_SP_I8 else torch.float32
+    if out is None:
+        out = torch.empty((m, n), dtype=want, device=ac.device)
+    elif tuple(out.shape) != (m, n) or out.dtype != want or not out.is_contiguous() or out.device != ac.device:
+        raise ValueError(f"out must be a contiguous {want} [M,N] tensor on the operands' GPU")
+    _check(load_library().odh_sparse_gemm(code, ac.data_ptr(), meta.data_ptr(), bt.data_ptr(), out.data_ptr(),
+                                          m, n, k, _stream_ptr(ac.device)))
+    return out
+
+
+def sparse_verify(fmt, ac, meta, bt, table) -> dict:
+    """The fused check of the given operands against ``table`` on a fresh counter block; the kernel's
+    time is taken with events around its one launch.  The dict of :func:`mx_verify` (``tflops`` counts
+    the dense-equivalent ``2·M·N·K``)."""
+    code, m, n, k = _sparse_operands(fmt, ac, meta, bt, probe=True)
+    _sparse_table(table, ac.device)
+
+    def launch(tile_xcd, counters, stream):
+        return load_library().odh_sparse_probe_gemm_verify(code, ac.data_ptr(), meta.data_ptr(), bt.data_ptr(),
+                                                           table.data_ptr(), m, n, k, tile_xcd, counters, stream)
+
+    return _fused_check(ac.device, m, n, k, launch)
+
+
+def sparse_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
+    """One structured-sparsity probe of a GPU: fill, then the GEMM with the check fused into its
+    epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
+    import torch
+
+    code = _sparse_format(fmt)
+    if not sparse_shape_ok(code, m, n, k) or sparse_zero_classes(k) != 0:
+        raise ValueError("sparse probe shape must be tile aligned, with a K at which no class expects 0")
+    dev = torch.device("cuda", device)
+    dtype = _sparse_dtype(code)
+    with torch.cuda.device(dev):
+        ac = torch.empty((m, k // 2), dtype=dtype, device=dev)
+        meta = torch.empty((m, k // 8), dtype=torch.uint8, device=dev)
+        bt = torch.empty((n, k), dtype=dtype, device=dev)
+        table = torch.empty(SPARSE_TABLE, dtype=torch.int32, device=dev)
+        sparse_fill(code, ac, meta, bt, table)
+        return sparse_verify(code, ac, meta, bt, table)
 
 
 class GpuProbe:
