@@ -52,6 +52,15 @@ enum {
   ODH_SP_FP8 = 3,   // OCP e4m3fn on both operands, 32x32x64, fp32 accumulation
   ODH_SP_BF8 = 4,   // OCP e5m2 on both operands, 32x32x64, fp32 accumulation
   ODH_SP_CLASSES = 210,  // ints in the table of expected values: (i mod 30, j mod 7)
+  // destination formats of the converter kernels (gpu_probe_cvt.h): the hardware's format codes again, and bf16
+  ODH_CVT_FP8 = 0,   // OCP e4m3fn
+  ODH_CVT_BF8 = 1,   // OCP e5m2
+  ODH_CVT_FP6 = 2,   // e2m3
+  ODH_CVT_BF6 = 3,   // e3m2
+  ODH_CVT_FP4 = 4,   // e2m1
+  ODH_CVT_BF16 = 5,  // bfloat16: no scale
+  ODH_CVT_BLOCKS = 256,  // workgroups of the fused check: one per CU
+  ODH_CVT_TABLE = 256,   // bytes of its scale table
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -135,6 +144,17 @@ int odh_sparse_gemm(int fmt, const void* Ac, const void* meta, const void* Bt, v
                     hipStream_t stream);
 int odh_sparse_probe_gemm_verify(int fmt, const void* Ac, const void* meta, const void* Bt, const int* table, int M,
                                  int N, int K, int* tile_xcd, int* counters, hipStream_t stream);
+// Converters (fmt: ODH_CVT_*): x [rows][K] f32, row-major, 16-byte aligned, K a multiple of 32; codes in the layout
+// odh_mx_gemm reads (FP8 / BF8 a byte per element, FP4 two per byte, FP6 / BF6 32 in 24 bytes), 8-byte aligned, or
+// [rows][K] bfloat16 for ODH_CVT_BF16, which takes no scales; scales [rows][K/32] E8M0 bytes.  The family of the
+// fused check: odh_cvt_family_size cases, of which odh_cvt_family writes n from first on as x (f32 bits), the
+// scale byte, the destination select in bits 8-9 of the same word, and the expected code, sign included
+unsigned odh_cvt_family_size(int fmt);  // host only (0: no such format)
+int odh_cvt_family(int fmt, unsigned first, unsigned n, uint32_t* x, uint32_t* scale, uint32_t* expect);  // host only; 0, or -1
+int odh_cvt_fill(int fmt, void* scale_table, hipStream_t stream);  // ODH_CVT_TABLE bytes
+int odh_cvt_encode(int fmt, const float* x, const void* scales, void* codes, long rows, long K, hipStream_t stream);
+int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, long rows, long K, hipStream_t stream);
+int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

@@ -43,6 +43,11 @@
 //    structured-sparsity path (v_smfmac_*: bf16, f16, i8, fp8, bf8; gpu_probe_sparse.h): compressed A,
 //    metadata and dense Bt on a three-slot ring, against a 30 × 7 table, and odh_sparse_zero_classes, the
 //    host-side guard against a K at which that check is blind.
+//  * odh_cvt_fill / odh_cvt_probe_verify — the converters that make low-precision codes at run time
+//    (v_cvt_scalef32_pk_fp8_f32 / _bf8_f32 / _fp4_f32, v_cvt_scalef32_2xpk16_fp6_f32 / _bf6_f32,
+//    v_cvt_pk_bf16_f32; gpu_probe_cvt.h): every rounding case of every code at every scale, on every SIMD,
+//    against codes known by construction; odh_cvt_family, the host's view of that family; and
+//    odh_cvt_quantize / odh_cvt_encode, f32 rows to OCP MX codes and scales in the layout odh_mx_gemm reads.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -834,6 +839,8 @@ int grid_for(size_t n, int per_block) {
   return (int)g;
 }
 
+#include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
+
 }  // namespace
 
 extern "C" {
@@ -1302,6 +1309,58 @@ int odh_sparse_probe_gemm_verify(int fmt, const void* Ac, const void* meta, cons
   sparse_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)Ac, (const uint32_t*)meta,
                            (const uint4*)Bt, (void*)nullptr, table, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
                            c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ converters (gpu_probe_cvt.h)
+
+// host only (no HIP call): the cases of a format's family (0: no such format), and cases [first, first + n)
+unsigned odh_cvt_family_size(int fmt) { return cvt_fmt_ok(fmt) ? cvt_family_size(fmt) : 0u; }
+
+int odh_cvt_family(int fmt, unsigned first, unsigned n, uint32_t* x, uint32_t* scale, uint32_t* expect) {
+  if (!cvt_fmt_ok(fmt) || !x || !scale || !expect || first > cvt_family_size(fmt) || n > cvt_family_size(fmt) - first)
+    return -1;
+  for (unsigned i = 0; i < n; ++i) {
+    const CvtCase c = cvt_case(fmt, first + i);
+    x[i] = c.x;
+    scale[i] = c.scale | c.sel << 8;
+    expect[i] = c.expect;
+  }
+  return 0;
+}
+
+// the table the fused check reads its scale bytes from (bf16: its exponent fields)
+int odh_cvt_fill(int fmt, void* scale_table, hipStream_t stream) {
+  if (!cvt_fmt_ok(fmt) || !scale_table) return (int)hipErrorInvalidValue;
+  cvt_fill_kernel<<<1, ODH_CVT_TABLE, 0, stream>>>(fmt, (uint8_t*)scale_table);
+  return (int)hipGetLastError();
+}
+
+// the bare instruction with the caller's scales (none for bf16)
+int odh_cvt_encode(int fmt, const float* x, const void* scales, void* codes, long rows, long K, hipStream_t stream) {
+  if (!cvt_rows_ok(fmt, x, codes, rows, K) || (cvt_scaled(fmt) && !scales)) return (int)hipErrorInvalidValue;
+  const size_t n = cvt_pieces(fmt, rows, K);
+  cvt_launch_rows<false>(fmt, grid_for(n, 1024), stream, (const cvt_f4*)x, n, (const uint8_t*)scales, codes,
+                         (uint8_t*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// OCP MX: the scales by the rule, the codes saturating (bf16: the plain conversion, scales_out unused)
+int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, long rows, long K, hipStream_t stream) {
+  if (!cvt_rows_ok(fmt, x, codes, rows, K) || (cvt_scaled(fmt) && !scales_out)) return (int)hipErrorInvalidValue;
+  const size_t n = cvt_pieces(fmt, rows, K);
+  cvt_launch_rows<true>(fmt, grid_for(n, 1024), stream, (const cvt_f4*)x, n, (const uint8_t*)nullptr, codes,
+                        (uint8_t*)scales_out);
+  return (int)hipGetLastError();
+}
+
+// every case of the family on every SIMD, against odh_cvt_fill's table; counters is a counter block of this
+// format's own (ODH_SLOT_XCD_BLOCKS, ODH_SLOT_ERR_XCD, ODH_SLOT_GEMM_ERR)
+int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream) {
+  if (!cvt_fmt_ok(fmt) || !scale_table || !counters) return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  cvt_launch_probe(fmt, stream, (const uint8_t*)scale_table, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR,
+                   c + ODH_SLOT_ERR_XCD);
   return (int)hipGetLastError();
 }
 

@@ -40,7 +40,12 @@
 //      before step 5, per format: the probe's A pruned 2:4 and compressed, its metadata and the dense Bt
 //      (odh_sparse_fill) into the operands' buffers, and the structured-sparsity GEMM (v_smfmac_*) checked
 //      in registers against a 30 × 7 table (odh_sparse_probe_gemm_verify): the index operand and the
-//      selection multiplexers a pruned model runs on, which no dense instruction touches.
+//      selection multiplexers a pruned model runs on, which no dense instruction touches;
+//   9. with --cvt fp8,bf8,fp4,fp6,bf6,bf16 (the `amd.com/gpu-probe: "cvt"` notebooks), after step 5, per format: the
+//      hardware converters that make those codes at run time (v_cvt_scalef32_pk_fp8_f32 and its kin,
+//      v_cvt_pk_bf16_f32), every rounding case of every code at every scale on every SIMD, compared in
+//      registers with codes known by construction (odh_cvt_probe_verify): no operand buffer, a 256-byte scale
+//      table (odh_cvt_fill) and a counter block per format.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -91,8 +96,9 @@ struct Slot {
   float ms = 0;
 };
 
-// An optional GEMM step (--mx, --dtypes, --fp, --sparse): per asked-for format, the probe operands re-encoded into
-// the bf16 operands' buffers and a fused check of that format's matrix-core instruction.
+// An optional step (--mx, --dtypes, --fp, --sparse: per asked-for format, the probe operands re-encoded into
+// the bf16 operands' buffers and a fused check of that format's matrix-core instruction; --cvt: per format, the
+// fused check of its converter).
 struct Step {
   const char* word;  // the option (--word), the --inject-fault word and the verdict key
   const char* what;  // in the error string: "<N> <what> mismatches"
@@ -101,6 +107,9 @@ struct Step {
   // verify, event, the counters copied back
   bool (*run)(Dev&, const Options&, int fmt, Slot&);
   int (*tiles)(int fmt, int M, int N) = nullptr;  // workgroups of a format's kernel; null: the bf16 GEMM's
+  double (*work)(int fmt) = nullptr;  // operations of a format's kernel; null: the GEMM's 2 M N K, reported as tflops
+  const char* rate = "tflops";        // the verdict key of the rate: with work, operations per nanosecond
+  bool host_ms = true;                // whether a format's entry ends with its host time
   std::vector<int> asked = {};  // the formats to check, in the order given
 
   const char* name(int fmt) const {
@@ -128,10 +137,14 @@ bool mx_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s);
+int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
+// conversions of the fused check: four waves in each of its workgroups convert the whole family
+double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --sparse, --mx
-enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, N_STEPS };
+// they run --dtypes, --fp, --sparse, --mx, --cvt
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -150,6 +163,12 @@ struct Options {
       {"sparse", "sparse GEMM",  // tflops counts the dense-equivalent 2 M N K
        {{"bf16", ODH_SP_BF16}, {"f16", ODH_SP_F16}, {"i8", ODH_SP_I8}, {"fp8", ODH_SP_FP8}, {"bf8", ODH_SP_BF8}},
        sp_run},
+      {"cvt", "conversion",  // gcvt_s: family cases per nanosecond over all waves
+       {{"fp8", ODH_CVT_FP8}, {"bf8", ODH_CVT_BF8}, {"fp4", ODH_CVT_FP4}, {"fp6", ODH_CVT_FP6}, {"bf6", ODH_CVT_BF6},
+        {"bf16", ODH_CVT_BF16}},
+       // no host_ms: with it the verdict of 8 healthy GPUs and every step is 3914 bytes at the widest, which one
+       // failing check's error string takes to the kubelet's 4096; its entries are 17 bytes shorter each
+       cvt_run, cvt_blocks, cvt_work, "gcvt_s", false},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -181,6 +200,8 @@ struct Dev {
   // --sparse: metadata and table behind those
   void* sp_meta = nullptr;
   int* sp_table = nullptr;
+  // --cvt: the scale table behind those
+  void* cvt_table = nullptr;
   std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
   std::string error;
 };
@@ -189,8 +210,9 @@ int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
                "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--sparse bf16,f16,i8,fp8,bf8] "
+               "[--cvt fp8,bf8,fp4,fp6,bf6,bf16] "
                "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
-               "[--inject-fault sparse] [--quiet]\n",
+               "[--inject-fault sparse] [--inject-fault cvt] [--quiet]\n",
                argv0);
   return 64;
 }
@@ -337,7 +359,8 @@ bool setup_alloc(Dev& d, const Options& o) {
   auto t0 = Clock::now();
   // every optional step adds a counter block per format behind the first; --mx also the scales of both
   // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
-  // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands)
+  // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
+  // --cvt adds its scale table
   size_t nslots = 0;
   for (const Step& s : o.steps) nslots += s.asked.size();
   const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
@@ -346,7 +369,8 @@ bool setup_alloc(Dev& d, const Options& o) {
   const bool sparse = !o.steps[STEP_SPARSE].asked.empty();
   const size_t nmeta = sparse ? align_up((size_t)o.M * (o.K / 8)) : 0;
   const size_t nsptab = sparse ? align_up(sizeof(int) * ODH_SP_CLASSES) : 0;
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab));
+  const size_t ncvt = o.steps[STEP_CVT].asked.empty() ? 0 : align_up(ODH_CVT_TABLE);
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -363,6 +387,7 @@ bool setup_alloc(Dev& d, const Options& o) {
     d.sp_meta = p + na + nb + nh + nt + nc + nsa + nsb + ntab;
     d.sp_table = (int*)(p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta);
   }
+  if (ncvt) d.cvt_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab;
   int* block = d.counters;
   for (int s = 0; s < N_STEPS; ++s) {
     d.slots[s].resize(o.steps[s].asked.size());
@@ -521,6 +546,22 @@ bool sp_run(Dev& d, const Options& o, int fmt, Slot& s) {
   HIP_TRY(hipEventRecord(s.e0, d.sh));
   HIP_TRY(odh_sparse_probe_gemm_verify(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, nullptr, s.counters,
                                        d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a format of --cvt, after --mx: its scale table, then the fused check of its converter
+bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_cvt_fill(fmt, d.cvt_table, d.sh));
+  if (o.fault == "cvt") {
+    // entry 3 of the table becomes 0 (the fill has at least 4 there): every case of that scale is divided by
+    // another power of two than the one it was multiplied by (bf16: gets another exponent than it expects)
+    HIP_TRY(hipMemsetAsync((char*)d.cvt_table + 3, 0, 1, d.sh));
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_cvt_probe_verify(fmt, d.cvt_table, s.counters, d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
@@ -788,11 +829,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, --sparse, then --mx: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, --sparse, --mx, then --cvt: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -904,7 +945,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[192] = "";  // N_STEPS entries of "word":ms,
+  char step_timing[240] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     for (size_t f = 0; f < s.asked.size(); ++f) {
@@ -934,11 +975,17 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
         }
       }
       ok = ok && fok;
-      char b[128];
-      std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"tflops\":%.1f,\"host_ms\":%.3f}",
-                    f ? "," : (std::string(",\"") + s.word + "\":{").c_str(), s.name(s.asked[f]),
-                    fok ? "true" : "false", (unsigned long long)errs, slowest,
-                    slowest > 0 ? flops / (slowest * 1e-3) / 1e12 : 0.0, step_host_ms[si][f]);
+      const double rate = slowest <= 0 ? 0.0
+                          : s.work     ? s.work(s.asked[f]) / (slowest * 1e6)
+                                       : flops / (slowest * 1e-3) / 1e12;
+      char b[160];
+      const int at = std::snprintf(b, sizeof b, "%s\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.4f,\"%s\":%.1f",
+                                   f ? "," : (std::string(",\"") + s.word + "\":{").c_str(), s.name(s.asked[f]),
+                                   fok ? "true" : "false", (unsigned long long)errs, slowest, s.rate, rate);
+      if (s.host_ms)
+        std::snprintf(b + at, sizeof b - at, ",\"host_ms\":%.3f}", step_host_ms[si][f]);
+      else
+        std::snprintf(b + at, sizeof b - at, "}");
       steps += b;
     }
     if (s.asked.empty()) continue;
@@ -947,7 +994,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     std::snprintf(step_timing + at, sizeof step_timing - at, "\"%s\":%.3f,", s.word, step_total_ms[si]);
   }
   for (Dev& d : devs) release(d);
-  char tail[512];
+  char tail[640];
   std::snprintf(tail, sizeof tail,
                 ",\"timings_ms\":{\"exec\":%.3f,\"hip_init\":%.3f,\"alloc_fill\":%.3f,\"alloc\":%.3f,"
                 "\"code_load\":%.3f,\"fill\":%.3f,\"probe\":%.3f,\"xgmi\":%.3f,\"rccl\":%.3f,%s\"total\":%.3f}}",

@@ -28,6 +28,10 @@
   (``v_smfmac_*`` on bf16, f16, int8, fp8 and bf8) on a compressed A, its metadata and a dense Bt: the
   same check against a 30 × 7 table (``odh-gpu-probe --sparse``); :func:`sparse_compress` and
   :func:`sparse_decompress` turn a dense tensor into that layout and back, in plain torch.
+* :func:`mx_quantize`, :func:`cvt_encode`, :func:`cvt_probe` — the hardware converters that make those codes
+  (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
+  layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
+  (``odh-gpu-probe --cvt``); :func:`cvt_family` is that check's family of inputs and expected codes.
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
@@ -104,8 +108,19 @@ ODH_SP_BF8 = 4  # OCP e5m2 on both operands, fp32 accumulation
 ODH_SP_CLASSES = 210  # ints in the table of expected values
 SPARSE_FORMATS = {"bf16": ODH_SP_BF16, "f16": ODH_SP_F16, "i8": ODH_SP_I8, "fp8": ODH_SP_FP8, "bf8": ODH_SP_BF8}
 SPARSE_TABLE = (30, 7)  # expected sums of the sparse probe operands, by (i mod 30, j mod 7)
+# destination formats of the converter kernels (csrc/gpu_probe_cvt.h): the hardware's format codes, and bf16
+ODH_CVT_FP8 = 0  # OCP e4m3fn
+ODH_CVT_BF8 = 1  # OCP e5m2
+ODH_CVT_FP6 = 2  # e2m3
+ODH_CVT_BF6 = 3  # e3m2
+ODH_CVT_FP4 = 4  # e2m1
+ODH_CVT_BF16 = 5  # bfloat16: no scale
+ODH_CVT_BLOCKS = 256  # workgroups of the fused check: one per CU
+ODH_CVT_TABLE = 256  # bytes of its scale table
+CVT_FORMATS = {"fp8": ODH_CVT_FP8, "bf8": ODH_CVT_BF8, "fp4": ODH_CVT_FP4, "fp6": ODH_CVT_FP6, "bf6": ODH_CVT_BF6,
+               "bf16": ODH_CVT_BF16}  # what ``--cvt`` checks, in its order
 
-_vp, _i, _u32, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
+_vp, _i, _u32, _sz, _long = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_long
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
 SIGNATURES = {
     "odh_gemm_shape_ok": (_i, [_i, _i, _i]),
@@ -150,6 +165,13 @@ SIGNATURES = {
     "odh_sparse_fill": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_sparse_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_sparse_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # converters (csrc/gpu_probe_cvt.h)
+    "odh_cvt_family_size": (_u32, [_i]),
+    "odh_cvt_family": (_i, [_i, _u32, _u32, _vp, _vp, _vp]),
+    "odh_cvt_fill": (_i, [_i, _vp, _vp]),
+    "odh_cvt_encode": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
+    "odh_cvt_quantize": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
+    "odh_cvt_probe_verify": (_i, [_i, _vp, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -803,6 +825,152 @@ def sparse_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE
         table = torch.empty(SPARSE_TABLE, dtype=torch.int32, device=dev)
         sparse_fill(code, ac, meta, bt, table)
         return sparse_verify(code, ac, meta, bt, table)
+
+
+def _cvt_format(fmt) -> int:
+    code = CVT_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in CVT_FORMATS.values():
+        raise ValueError(f"converter format must be one of {sorted(CVT_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def cvt_family_size(fmt) -> int:
+    """Cases of the family the fused converter check walks.  Host arithmetic only."""
+    return load_library().odh_cvt_family_size(_cvt_format(fmt))
+
+
+def cvt_family(fmt, first: int = 0, n: Optional[int] = None) -> dict:
+    """Cases ``[first, first + n)`` of the family of ``fmt`` (all of it by default), from the library's own
+    generator, as CPU tensors: ``x`` float32 inputs, ``scale`` the E8M0 byte of each (127 for bf16), ``sel``
+    the destination select, ``expect`` the code with its sign (int32; 16 bits for bf16).  32 consecutive
+    cases from a multiple of 32 on share their scale.  Host arithmetic only."""
+    import torch
+
+    code = _cvt_format(fmt)
+    size = cvt_family_size(code)
+    if n is None:
+        n = size - first
+    if first < 0 or n < 0 or first + n > size:
+        raise ValueError(f"cases [{first}, {first + n}) are not in the family of {size}")
+    x, sc, ex = (torch.empty((n,), dtype=torch.int32) for _ in range(3))
+    if load_library().odh_cvt_family(code, first, n, x.data_ptr(), sc.data_ptr(), ex.data_ptr()) != 0:
+        raise ValueError("odh_cvt_family refused its arguments")
+    return {"x": x.view(torch.float32), "scale": (sc & 255).to(torch.uint8), "sel": (sc >> 8).to(torch.uint8),
+            "expect": ex}
+
+
+def _cvt_rows(fmt, x, scales=None):
+    """Checks of the converter entry points, before launch: ``x`` float32 ``[rows, K]`` on a GPU, contiguous,
+    16-byte aligned, K a multiple of 32; ``scales`` (if given) uint8 ``[rows, K/32]`` on the same GPU.
+    Returns the format code, rows, K."""
+    import torch
+
+    code = _cvt_format(fmt)
+    if x.dtype != torch.float32 or (scales is not None and scales.dtype != torch.uint8):
+        raise ValueError("the converters take float32 values and uint8 scales")
+    if x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x must be a contiguous 2-D tensor on a GPU")
+    rows, k = x.shape
+    if rows < 1 or k < 32 or k % 32:
+        raise ValueError(f"x must be [rows >= 1, K a positive multiple of 32]; got {tuple(x.shape)}")
+    if x.data_ptr() % 16:
+        raise ValueError("x must be 16-byte aligned")
+    if scales is not None:
+        if code == ODH_CVT_BF16:
+            raise ValueError("bf16 takes no scales")
+        if not scales.is_cuda or scales.device != x.device or not scales.is_contiguous() \
+                or tuple(scales.shape) != (rows, k // 32):
+            raise ValueError(f"scales must be a contiguous [{rows},{k // 32}] tensor on x's GPU")
+    return code, rows, k
+
+
+def _cvt_out(code: int, x, rows: int, k: int):
+    import torch
+
+    if code == ODH_CVT_BF16:
+        return torch.empty((rows, k), dtype=torch.bfloat16, device=x.device)
+    return torch.empty((rows, mx_row_bytes(code, k)), dtype=torch.uint8, device=x.device)
+
+
+def cvt_encode(fmt, x, scales=None):
+    """The hardware converter as it is: ``x`` ``[rows, K]`` float32 divided by the caller's E8M0 ``scales``
+    ``[rows, K/32]`` and rounded to nearest even, to uint8 codes in the layout :func:`mx_gemm` reads
+    (``[rows, mx_row_bytes]``); what lies beyond the largest finite value becomes what the instruction makes
+    of it.  ``"bf16"`` takes no scales and returns a bfloat16 ``[rows, K]`` tensor."""
+    code, rows, k = _cvt_rows(fmt, x, scales)
+    if code != ODH_CVT_BF16 and scales is None:
+        raise ValueError("the scaled formats need scales")
+    out = _cvt_out(code, x, rows, k)
+    _check(load_library().odh_cvt_encode(code, x.data_ptr(), scales.data_ptr() if scales is not None else None,
+                                         out.data_ptr(), rows, k, _stream_ptr(x.device)))
+    return out
+
+
+def mx_quantize(fmt, x):
+    """OCP MX quantisation on the GPU: ``x`` ``[rows, K]`` float32 to ``(codes, scales)`` as :func:`mx_gemm`
+    takes them.  The scale of a block of 32 is ``2^(floor(log2(amax)) - emax)`` of the element format, clamped
+    to E8M0 (2^0 for an all-zero block); the elements go through the hardware converter with that scale and
+    saturate at the largest finite code.  ``"bf16"`` is the plain conversion: ``(bfloat16 tensor, None)``."""
+    import torch
+
+    code, rows, k = _cvt_rows(fmt, x)
+    out = _cvt_out(code, x, rows, k)
+    scales = None if code == ODH_CVT_BF16 else torch.empty((rows, k // 32), dtype=torch.uint8, device=x.device)
+    _check(load_library().odh_cvt_quantize(code, x.data_ptr(), out.data_ptr(),
+                                           scales.data_ptr() if scales is not None else None, rows, k,
+                                           _stream_ptr(x.device)))
+    return out, scales
+
+
+def cvt_fill(fmt, table) -> None:
+    """The scale table of the fused converter check (``ODH_CVT_TABLE`` uint8) written into ``table``."""
+    import torch
+
+    code = _cvt_format(fmt)
+    if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_CVT_TABLE,) or not table.is_cuda \
+            or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 [{ODH_CVT_TABLE}] tensor on a GPU")
+    _check(load_library().odh_cvt_fill(code, table.data_ptr(), _stream_ptr(table.device)))
+
+
+def cvt_verify(fmt, table) -> dict:
+    """The fused check against ``table`` on a fresh counter block: every wave of ``ODH_CVT_BLOCKS`` workgroups
+    converts the whole family.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms``, and ``gcvt_s``, family cases
+    per nanosecond over all waves."""
+    import torch
+
+    code = _cvt_format(fmt)
+    if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_CVT_TABLE,) or not table.is_cuda \
+            or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 [{ODH_CVT_TABLE}] tensor on a GPU")
+    dev = table.device
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load_library().odh_cvt_probe_verify(code, table.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    ms = e0.elapsed_time(e1)
+    return {
+        "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
+        "ms": ms, "gcvt_s": cvt_family_size(code) * ODH_CVT_BLOCKS * 4 / (ms * 1e6) if ms > 0 else 0.0,
+    }
+
+
+def cvt_probe(device: int, fmt) -> dict:
+    """One converter probe of a GPU: the scale table, then the fused check.  The dict of :func:`cvt_verify`."""
+    import torch
+
+    code = _cvt_format(fmt)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        table = torch.empty((ODH_CVT_TABLE,), dtype=torch.uint8, device=dev)
+        cvt_fill(code, table)
+        return cvt_verify(code, table)
 
 
 class GpuProbe:
