@@ -44,7 +44,8 @@ def targets() -> Dict[str, dict]:
             "src": [os.path.join(CSRC, "gpu_probe.hip"), os.path.join(CSRC, "probe_cli.cpp")],
             "deps": [os.path.join(CSRC, "gpu_probe.h"), os.path.join(CSRC, "gpu_probe_mx.h"),
                      os.path.join(CSRC, "gpu_probe_dense.h"), os.path.join(CSRC, "gpu_probe_fp.h"),
-                     os.path.join(CSRC, "gpu_probe_sparse.h"), os.path.join(CSRC, "gpu_probe_cvt.h")],
+                     os.path.join(CSRC, "gpu_probe_sparse.h"), os.path.join(CSRC, "gpu_probe_cvt.h"),
+                     os.path.join(CSRC, "gpu_probe_lds.h")],
             "cmd": lambda src, out: [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
                                      *src, "-o", out],
         },

@@ -61,6 +61,22 @@ enum {
   ODH_CVT_BF16 = 5,  // bfloat16: no scale
   ODH_CVT_BLOCKS = 256,  // workgroups of the fused check: one per CU
   ODH_CVT_TABLE = 256,   // bytes of its scale table
+  // checks of the LDS step (gpu_probe_lds.h)
+  ODH_LDS_MEM = 0,    // every dword of a CU's 160 KiB, written and read in different widths by different waves
+  ODH_LDS_TR16 = 1,   // ds_read_b64_tr_b16
+  ODH_LDS_TR8 = 2,    // ds_read_b64_tr_b8
+  ODH_LDS_TR4 = 3,    // ds_read_b64_tr_b4
+  ODH_LDS_TR6 = 4,    // ds_read_b96_tr_b6
+  ODH_LDS_XLANE = 5,  // ds_bpermute / ds_permute / ds_swizzle, DPP, v_readlane / v_writelane, v_permlane16/32_swap
+  ODH_LDS_BLOCKS = 256,   // workgroups of a fused check: one per CU
+  ODH_LDS_TABLE = 1024,   // bytes of its key table
+  ODH_LDS_CU_WORDS = 64,  // dwords of the bitmap of CUs behind a counter block: bit XCC_ID << 8 | SE_ID << 5 | SH_ID << 4 | CU_ID
+  ODH_LDS_TR_RAW = 256,   // added to odh_lds_tr_read's check: the alignment of the addresses is not checked (measuring)
+  // element formats of odh_transpose_codes
+  ODH_TC_B16 = 0,  // 16-bit elements (bf16, f16)
+  ODH_TC_B8 = 1,   // one byte per element (fp8, bf8, E8M0 scales)
+  ODH_TC_B4 = 2,   // two nibbles per byte, even index low (fp4)
+  ODH_TC_B6 = 3,   // element k in bits [6k, 6k + 6) of a row (fp6, bf6)
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -155,6 +171,24 @@ int odh_cvt_fill(int fmt, void* scale_table, hipStream_t stream);  // ODH_CVT_TA
 int odh_cvt_encode(int fmt, const float* x, const void* scales, void* codes, long rows, long K, hipStream_t stream);
 int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, long rows, long K, hipStream_t stream);
 int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream);
+// The LDS step (check: ODH_LDS_*; gpu_probe_lds.h).  table: ODH_LDS_TABLE bytes on the device, 4-byte aligned;
+// counters: ODH_NCOUNT × i32 of this check's own (slots as for the converters) and ODH_LDS_CU_WORDS dwords behind
+// them, the bitmap of the CUs the workgroups ran on.  odh_lds_tr_read: one wave, one transposing read; image
+// (bytes of it, a multiple of 4, at most 65536) is copied to LDS, lane l reads at byte address lane_addr[l] (64
+// of them, on the host) and stores its 8 or 12 result bytes at out + 8 l or out + 12 l; addresses out of range, or
+// misaligned for the instruction unless ODH_LDS_TR_RAW is added to check, are refused.  odh_lds_xlane: one
+// wave, one exchange of the 64 values in (the two swaps: of 128, lane l's second register at 64 + l) into out;
+// op 0 … 7: ds_bpermute, ds_permute, ds_swizzle, DPP, v_readlane, v_writelane, v_permlane16_swap,
+// v_permlane32_swap; arg: its selector (gpu_probe_lds.h).  odh_transpose_codes (fmt: ODH_TC_*): src [R][C]
+// elements, row-major and packed, to dst [C][R]; R and C multiples of 128, both buffers 16-byte aligned
+unsigned long long odh_lds_cases(int check);  // host only: elements compared per launch (0: no such check)
+unsigned long long odh_lds_fault_count(int check, int table_byte);  // host only: mismatches when that byte is wrong
+int odh_lds_fill(int check, void* table, hipStream_t stream);
+int odh_lds_probe_verify(int check, const void* table, int* counters, hipStream_t stream);
+int odh_lds_tr_read(int check, const void* image, unsigned bytes, const uint32_t* lane_addr, void* out,
+                    hipStream_t stream);
+int odh_lds_xlane(int op, int arg, const uint32_t* in, uint32_t* out, hipStream_t stream);
+int odh_transpose_codes(int fmt, const void* src, void* dst, long R, long C, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);

@@ -48,6 +48,12 @@
 //    v_cvt_pk_bf16_f32; gpu_probe_cvt.h): every rounding case of every code at every scale, on every SIMD,
 //    against codes known by construction; odh_cvt_family, the host's view of that family; and
 //    odh_cvt_quantize / odh_cvt_encode, f32 rows to OCP MX codes and scales in the layout odh_mx_gemm reads.
+//  * odh_lds_fill / odh_lds_probe_verify — the LDS itself, the transposing LDS reads (ds_read_b64_tr_b16 / _b8 /
+//    _b4, ds_read_b96_tr_b6) and the lane exchanges (ds_bpermute, ds_swizzle, DPP, v_readlane, v_permlane32_swap and
+//    their kin; gpu_probe_lds.h), one workgroup per CU, against closed forms; odh_lds_cases and
+//    odh_lds_fault_count, the host's view of what they compare; odh_lds_tr_read and odh_lds_xlane, one
+//    instruction at a time, which the lane maps were measured with; and odh_transpose_codes, packed codes [R][C]
+//    to [C][R] through those reads.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -58,6 +64,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <utility>
 
 #include "gpu_probe.h"
 
@@ -840,6 +847,7 @@ int grid_for(size_t n, int per_block) {
 }
 
 #include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
+#include "gpu_probe_lds.h"  // the LDS, its transposing reads, the lane exchanges and the transposer of packed codes
 
 }  // namespace
 
@@ -1361,6 +1369,68 @@ int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStr
   unsigned* c = (unsigned*)counters;
   cvt_launch_probe(fmt, stream, (const uint8_t*)scale_table, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR,
                    c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ LDS step (gpu_probe_lds.h)
+
+// host only (no HIP call): elements compared per launch, and of those the ones that use the key dword of a table byte
+unsigned long long odh_lds_cases(int check) {
+  return lds_check_ok(check) ? lds_block_cases(check, -1) * ODH_LDS_BLOCKS : 0ull;
+}
+
+unsigned long long odh_lds_fault_count(int check, int table_byte) {
+  if (!lds_check_ok(check) || table_byte < 0 || table_byte >= ODH_LDS_TABLE) return 0ull;
+  return lds_block_cases(check, table_byte / 4) * ODH_LDS_BLOCKS;
+}
+
+int odh_lds_fill(int check, void* table, hipStream_t stream) {
+  if (!lds_check_ok(check) || !table || ((uintptr_t)table & 3)) return (int)hipErrorInvalidValue;
+  lds_fill_kernel<<<1, ODH_LDS_TABLE / 4, 0, stream>>>(check, (uint32_t*)table);
+  return (int)hipGetLastError();
+}
+
+// a fused check against odh_lds_fill's table; counters is a counter block of this check's own with the CU
+// bitmap behind it (ODH_NCOUNT + ODH_LDS_CU_WORDS dwords)
+int odh_lds_probe_verify(int check, const void* table, int* counters, hipStream_t stream) {
+  if (!lds_check_ok(check) || !table || ((uintptr_t)table & 3) || !counters) return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  lds_launch_probe(check, stream, (const uint32_t*)table, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR,
+                   c + ODH_SLOT_ERR_XCD, c + ODH_NCOUNT);
+  return (int)hipGetLastError();
+}
+
+int odh_lds_tr_read(int check, const void* image, unsigned bytes, const uint32_t* lane_addr, void* out,
+                    hipStream_t stream) {
+  const bool raw = check >= ODH_LDS_TR_RAW;
+  if (raw) check -= ODH_LDS_TR_RAW;
+  if (!lds_is_tr(check) || !image || !lane_addr || !out || bytes == 0 || bytes > 65536 || bytes % 4 ||
+      ((uintptr_t)image & 3) || ((uintptr_t)out & 3))
+    return (int)hipErrorInvalidValue;
+  const LdsTr s = lds_tr_spec(check);
+  LdsLaneAddr a;
+  for (int l = 0; l < 64; ++l) {
+    a.a[l] = lane_addr[l];
+    if (a.a[l] > bytes || 4u * s.words > bytes - a.a[l] || (!raw && a.a[l] % s.align)) return (int)hipErrorInvalidValue;
+  }
+  lds_launch_tr_read(check, (bytes + 15u) & ~15u, stream, (const uint32_t*)image, bytes, a, (uint32_t*)out);
+  return (int)hipGetLastError();
+}
+
+int odh_lds_xlane(int op, int arg, const uint32_t* in, uint32_t* out, hipStream_t stream) {
+  if (op < 0 || op >= LDS_XL_OPS || arg < 0 || arg >= lds_xl_args(op) || !in || !out) return (int)hipErrorInvalidValue;
+  lds_xlane_one_kernel<<<1, 64, 0, stream>>>(op, arg, in, out);
+  return (int)hipGetLastError();
+}
+
+// packed codes [R][C] to [C][R]; the format and the shape are checked before the pointers
+int odh_transpose_codes(int fmt, const void* src, void* dst, long R, long C, hipStream_t stream) {
+  if (!lds_tc_ok(fmt) || R <= 0 || C <= 0 || R % LDS_TC_TILE || C % LDS_TC_TILE || R > (1L << 40) / C ||
+      (R / LDS_TC_TILE) * (C / LDS_TC_TILE) > 0x7FFFFFFFL || !src || !dst || ((uintptr_t)src & 15) ||
+      ((uintptr_t)dst & 15) || src == dst)
+    return (int)hipErrorInvalidValue;
+  lds_launch_transpose(fmt, (unsigned)((R / LDS_TC_TILE) * (C / LDS_TC_TILE)), stream, (const unsigned char*)src,
+                       (unsigned char*)dst, R, C);
   return (int)hipGetLastError();
 }
 

@@ -45,7 +45,13 @@
 //      hardware converters that make those codes at run time (v_cvt_scalef32_pk_fp8_f32 and its kin,
 //      v_cvt_pk_bf16_f32), every rounding case of every code at every scale on every SIMD, compared in
 //      registers with codes known by construction (odh_cvt_probe_verify): no operand buffer, a 256-byte scale
-//      table (odh_cvt_fill) and a counter block per format.
+//      table (odh_cvt_fill) and a counter block per format;
+//  10. with --lds mem,tr16,tr8,tr4,tr6,xlane (the `amd.com/gpu-probe: "lds"` notebooks), after step 9, per check: every
+//      dword of every CU's 160 KiB of LDS, the transposing LDS reads (ds_read_b64_tr_b16 / _b8 / _b4,
+//      ds_read_b96_tr_b6) and the lane exchanges (ds_bpermute, ds_swizzle, DPP, v_readlane, v_permlane32_swap and
+//      their kin), one workgroup per CU and one wave per SIMD, compared in registers with closed forms
+//      (odh_lds_probe_verify): no operand buffer, a 1 KiB key table (odh_lds_fill) and a counter block per check.
+//      Its verdict is one entry for the whole step: "lds":{"ok","errors","ms","bad"}.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -110,6 +116,7 @@ struct Step {
   double (*work)(int fmt) = nullptr;  // operations of a format's kernel; null: the GEMM's 2 M N K, reported as tflops
   const char* rate = "tflops";        // the verdict key of the rate: with work, operations per nanosecond
   bool host_ms = true;                // whether a format's entry ends with its host time
+  bool flat = false;                  // one entry for the whole step instead of one per format (--lds)
   std::vector<int> asked = {};  // the formats to check, in the order given
 
   const char* name(int fmt) const {
@@ -138,13 +145,15 @@ bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool lds_run(Dev& d, const Options& o, int check, Slot& s);
+int lds_blocks(int, int, int) { return ODH_LDS_BLOCKS; }
 int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
 // conversions of the fused check: four waves in each of its workgroups convert the whole family
 double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --sparse, --mx, --cvt
-enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, N_STEPS };
+// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -169,6 +178,11 @@ struct Options {
        // no host_ms: with it the verdict of 8 healthy GPUs and every step is 3914 bytes at the widest, which one
        // failing check's error string takes to the kubelet's 4096; its entries are 17 bytes shorter each
        cvt_run, cvt_blocks, cvt_work, "gcvt_s", false},
+      {"lds", "LDS",
+       {{"mem", ODH_LDS_MEM}, {"tr16", ODH_LDS_TR16}, {"tr8", ODH_LDS_TR8}, {"tr4", ODH_LDS_TR4}, {"tr6", ODH_LDS_TR6},
+        {"xlane", ODH_LDS_XLANE}},
+       // flat: six more entries would not fit the kubelet's 4096 bytes next to every other step on 8 GPUs
+       lds_run, lds_blocks, nullptr, "", false, true},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -202,6 +216,8 @@ struct Dev {
   int* sp_table = nullptr;
   // --cvt: the scale table behind those
   void* cvt_table = nullptr;
+  // --lds: its key table behind that, and its counter blocks (each with the CU bitmap) behind the table
+  void* lds_table = nullptr;
   std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
   std::string error;
 };
@@ -210,9 +226,9 @@ int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s [--json PATH|-] [--shape M,N,K] [--hbm-mib N] [--xgmi-mib N] [--rccl-mib N] "
                "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--sparse bf16,f16,i8,fp8,bf8] "
-               "[--cvt fp8,bf8,fp4,fp6,bf6,bf16] "
+               "[--cvt fp8,bf8,fp4,fp6,bf6,bf16] [--lds mem,tr16,tr8,tr4,tr6,xlane] "
                "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
-               "[--inject-fault sparse] [--inject-fault cvt] [--quiet]\n",
+               "[--inject-fault sparse] [--inject-fault cvt] [--inject-fault lds] [--quiet]\n",
                argv0);
   return 64;
 }
@@ -360,9 +376,13 @@ bool setup_alloc(Dev& d, const Options& o) {
   // every optional step adds a counter block per format behind the first; --mx also the scales of both
   // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
   // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
-  // --cvt adds its scale table
+  // --cvt adds its scale table; --lds its key table and counter blocks of its own size, with the CU bitmap
   size_t nslots = 0;
-  for (const Step& s : o.steps) nslots += s.asked.size();
+  for (const Step& s : o.steps)
+    if (!s.flat) nslots += s.asked.size();
+  const size_t nlds_asked = o.steps[STEP_LDS].asked.size();
+  const size_t lds_block = sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS);
+  const size_t nldstab = nlds_asked ? align_up(ODH_LDS_TABLE) : 0, nldsc = nlds_asked ? align_up(lds_block * nlds_asked) : 0;
   const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
@@ -370,7 +390,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t nmeta = sparse ? align_up((size_t)o.M * (o.K / 8)) : 0;
   const size_t nsptab = sparse ? align_up(sizeof(int) * ODH_SP_CLASSES) : 0;
   const size_t ncvt = o.steps[STEP_CVT].asked.empty() ? 0 : align_up(ODH_CVT_TABLE);
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt));
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -388,11 +408,15 @@ bool setup_alloc(Dev& d, const Options& o) {
     d.sp_table = (int*)(p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta);
   }
   if (ncvt) d.cvt_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab;
+  if (nlds_asked) d.lds_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt;
   int* block = d.counters;
   for (int s = 0; s < N_STEPS; ++s) {
     d.slots[s].resize(o.steps[s].asked.size());
+    if (s == STEP_LDS) continue;
     for (Slot& slot : d.slots[s]) slot.counters = block += ODH_NCOUNT;
   }
+  for (size_t f = 0; f < nlds_asked; ++f)
+    d.slots[STEP_LDS][f].counters = (int*)((char*)d.lds_table + nldstab + lds_block * f);
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -562,6 +586,26 @@ bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s) {
   }
   HIP_TRY(hipEventRecord(s.e0, d.sh));
   HIP_TRY(odh_cvt_probe_verify(fmt, d.cvt_table, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a check of --lds, after --cvt: its key table, then the fused check; the counter block is cleared here
+bool lds_run(Dev& d, const Options& o, int check, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS), d.sh));
+  HIP_TRY(odh_lds_fill(check, d.lds_table, d.sh));
+  if (o.fault == "lds") {
+    // bit 0 of byte 5 of the table flips (a change a 4- or 6-bit element cannot miss): everything stored with
+    // key dword 1 differs from what the kernel expects of it
+    unsigned char byte = 0;
+    HIP_TRY(hipMemcpyAsync(&byte, (char*)d.lds_table + 5, 1, hipMemcpyDeviceToHost, d.sh));
+    HIP_TRY(hipStreamSynchronize(d.sh));
+    HIP_TRY(hipMemsetAsync((char*)d.lds_table + 5, byte ^ 1, 1, d.sh));
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_lds_probe_verify(check, d.lds_table, s.counters, d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
@@ -829,11 +873,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, --sparse, --mx, then --cvt: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, --sparse, --mx, --cvt, then --lds: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -945,9 +989,14 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[240] = "";  // N_STEPS entries of "word":ms,
+  char step_timing[288] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
+    // a flat step: total mismatches, the slowest device's kernel time summed over the checks, and the checks
+    // that counted mismatches or missed workgroups
+    uint64_t flat_errs = 0;
+    std::string flat_bad;
+    std::vector<float> flat_ms(devs.size(), 0.f);
     for (size_t f = 0; f < s.asked.size(); ++f) {
       const int ftiles = s.tiles ? s.tiles(s.asked[f], o.M, o.N) : tiles;
       uint64_t errs = 0;
@@ -969,12 +1018,19 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
         fok = false;
         if (first_err.empty()) {
           char b[200];
-          std::snprintf(b, sizeof b, "GPU %d: %s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index,
-                        s.name(s.asked[f]), e, s.what, where.empty() ? "-" : where.c_str(), blocks, ftiles);
+          std::snprintf(b, sizeof b, "GPU %d: %s%s%s: %u %s mismatches on XCD %s, %ld/%d tiles", d.index,
+                        s.flat ? s.word : "", s.flat ? " " : "", s.name(s.asked[f]), e, s.what,
+                        where.empty() ? "-" : where.c_str(), blocks, ftiles);
           first_err = b;
         }
       }
       ok = ok && fok;
+      if (s.flat) {
+        flat_errs += errs;
+        if (!fok) flat_bad += (flat_bad.empty() ? "" : ",") + std::string(s.name(s.asked[f]));
+        for (size_t di = 0; di < devs.size(); ++di) flat_ms[di] += devs[di].slots[si][f].ms;
+        continue;
+      }
       const double rate = slowest <= 0 ? 0.0
                           : s.work     ? s.work(s.asked[f]) / (slowest * 1e6)
                                        : flops / (slowest * 1e-3) / 1e12;
@@ -989,6 +1045,13 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
       steps += b;
     }
     if (s.asked.empty()) continue;
+    if (s.flat) {
+      char b[200];
+      std::snprintf(b, sizeof b, ",\"%s\":{\"ok\":%s,\"errors\":%llu,\"ms\":%.3f,\"bad\":\"%s\"", s.word,
+                    flat_bad.empty() ? "true" : "false", (unsigned long long)flat_errs,
+                    *std::max_element(flat_ms.begin(), flat_ms.end()), flat_bad.c_str());
+      steps += b;
+    }
     steps += "}";
     const size_t at = std::strlen(step_timing);
     std::snprintf(step_timing + at, sizeof step_timing - at, "\"%s\":%.3f,", s.word, step_total_ms[si]);

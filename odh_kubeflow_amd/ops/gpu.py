@@ -28,6 +28,9 @@
   (``v_smfmac_*`` on bf16, f16, int8, fp8 and bf8) on a compressed A, its metadata and a dense Bt: the
   same check against a 30 × 7 table (``odh-gpu-probe --sparse``); :func:`sparse_compress` and
   :func:`sparse_decompress` turn a dense tensor into that layout and back, in plain torch.
+* :func:`lds_probe`, :func:`lds_tr_read`, :func:`lds_xlane`, :func:`transpose_codes`, :func:`mx_transpose` — the LDS
+  itself, the transposing LDS reads (``ds_read_b64_tr_b16`` / ``_b8`` / ``_b4``, ``ds_read_b96_tr_b6``) and the lane
+  exchanges (``odh-gpu-probe --lds``), and the transposer of packed codes built on those reads.
 * :func:`mx_quantize`, :func:`cvt_encode`, :func:`cvt_probe` — the hardware converters that make those codes
   (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
   layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
@@ -120,6 +123,32 @@ ODH_CVT_TABLE = 256  # bytes of its scale table
 CVT_FORMATS = {"fp8": ODH_CVT_FP8, "bf8": ODH_CVT_BF8, "fp4": ODH_CVT_FP4, "fp6": ODH_CVT_FP6, "bf6": ODH_CVT_BF6,
                "bf16": ODH_CVT_BF16}  # what ``--cvt`` checks, in its order
 
+# checks of the LDS step (csrc/gpu_probe_lds.h)
+ODH_LDS_MEM = 0  # every dword of a CU's 160 KiB, written and read in different widths by different waves
+ODH_LDS_TR16 = 1  # ds_read_b64_tr_b16
+ODH_LDS_TR8 = 2  # ds_read_b64_tr_b8
+ODH_LDS_TR4 = 3  # ds_read_b64_tr_b4
+ODH_LDS_TR6 = 4  # ds_read_b96_tr_b6
+ODH_LDS_XLANE = 5  # ds_bpermute / ds_permute / ds_swizzle, DPP, v_readlane / v_writelane, v_permlane16/32_swap
+ODH_LDS_BLOCKS = 256  # workgroups of a fused check: one per CU
+ODH_LDS_TABLE = 1024  # bytes of its key table
+ODH_LDS_CU_WORDS = 64  # dwords of the bitmap of CUs behind a counter block
+ODH_LDS_TR_RAW = 256  # added to odh_lds_tr_read's check: the alignment of the addresses is not checked (measuring)
+# element formats of odh_transpose_codes
+ODH_TC_B16 = 0  # 16-bit elements
+ODH_TC_B8 = 1  # one byte per element
+ODH_TC_B4 = 2  # two nibbles per byte, even index low
+ODH_TC_B6 = 3  # element k in bits [6k, 6k + 6) of a row
+LDS_CHECKS = {"mem": ODH_LDS_MEM, "tr16": ODH_LDS_TR16, "tr8": ODH_LDS_TR8, "tr4": ODH_LDS_TR4, "tr6": ODH_LDS_TR6,
+              "xlane": ODH_LDS_XLANE}  # what ``--lds`` checks, in its order
+LDS_XLANE_OPS = {"bpermute": 0, "permute": 1, "swizzle": 2, "dpp": 3, "readlane": 4, "writelane": 5,
+                 "permlane16_swap": 6, "permlane32_swap": 7}  # ``op`` of :func:`lds_xlane`
+LDS_XLANE_ARGS = {"bpermute": 65, "permute": 65, "swizzle": 12, "dpp": 55, "readlane": 64, "writelane": 64,
+                  "permlane16_swap": 4, "permlane32_swap": 4}  # selectors of each
+# format -> (element format of the transposer, bits of an element)
+TRANSPOSE_FORMATS = {"bf16": (ODH_TC_B16, 16), "f16": (ODH_TC_B16, 16), "fp8": (ODH_TC_B8, 8), "bf8": (ODH_TC_B8, 8),
+                     "fp4": (ODH_TC_B4, 4), "fp6": (ODH_TC_B6, 6), "bf6": (ODH_TC_B6, 6)}
+
 _vp, _i, _u32, _sz, _long = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_long
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
 SIGNATURES = {
@@ -172,6 +201,14 @@ SIGNATURES = {
     "odh_cvt_encode": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_quantize": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_probe_verify": (_i, [_i, _vp, _vp, _vp]),
+    # the LDS step and the transposer of packed codes (csrc/gpu_probe_lds.h)
+    "odh_lds_cases": (ctypes.c_ulonglong, [_i]),
+    "odh_lds_fault_count": (ctypes.c_ulonglong, [_i, _i]),
+    "odh_lds_fill": (_i, [_i, _vp, _vp]),
+    "odh_lds_probe_verify": (_i, [_i, _vp, _vp, _vp]),
+    "odh_lds_tr_read": (_i, [_i, _vp, ctypes.c_uint, _vp, _vp, _vp]),
+    "odh_lds_xlane": (_i, [_i, _i, _vp, _vp, _vp]),
+    "odh_transpose_codes": (_i, [_i, _vp, _vp, _long, _long, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -971,6 +1008,182 @@ def cvt_probe(device: int, fmt) -> dict:
         table = torch.empty((ODH_CVT_TABLE,), dtype=torch.uint8, device=dev)
         cvt_fill(code, table)
         return cvt_verify(code, table)
+
+
+def _lds_check(check) -> int:
+    code = LDS_CHECKS.get(check, check) if isinstance(check, str) else check
+    if isinstance(code, bool) or code not in LDS_CHECKS.values():
+        raise ValueError(f"LDS check must be one of {sorted(LDS_CHECKS)}; got {check!r}")
+    return code
+
+
+def lds_cases(check) -> int:
+    """Elements one launch of the fused check compares.  Host arithmetic only."""
+    return load_library().odh_lds_cases(_lds_check(check))
+
+
+def lds_fault_count(check, table_byte: int) -> int:
+    """Mismatches the fused check counts when byte ``table_byte`` of its key table is wrong (for ``tr4`` and
+    ``tr6``: wrong in another way in its low nibble than in its high one).  Host arithmetic only."""
+    code = _lds_check(check)
+    if not 0 <= table_byte < ODH_LDS_TABLE:
+        raise ValueError(f"table_byte must be in [0, {ODH_LDS_TABLE}); got {table_byte}")
+    return load_library().odh_lds_fault_count(code, table_byte)
+
+
+def _lds_table(table) -> None:
+    import torch
+
+    if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_LDS_TABLE,) or not table.is_cuda \
+            or not table.is_contiguous() or table.data_ptr() % 4:
+        raise ValueError(f"table must be a contiguous, 4-byte aligned uint8 [{ODH_LDS_TABLE}] tensor on a GPU")
+
+
+def lds_fill(check, table) -> None:
+    """The key table of a fused LDS check (``ODH_LDS_TABLE`` uint8) written into ``table``."""
+    code = _lds_check(check)
+    _lds_table(table)
+    _check(load_library().odh_lds_fill(code, table.data_ptr(), _stream_ptr(table.device)))
+
+
+def lds_verify(check, table) -> dict:
+    """The fused check against ``table`` on a fresh counter block: ``ODH_LDS_BLOCKS`` workgroups, one wave per
+    SIMD.  ``ok`` (no mismatch and every workgroup ran), ``errors``, ``blocks``, ``err_xcd``, ``xcd_blocks``,
+    ``ms``, and ``cus``: the distinct CUs the workgroups reported, which is recorded and no part of ``ok``."""
+    import torch
+
+    code = _lds_check(check)
+    _lds_table(table)
+    dev = table.device
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT + ODH_LDS_CU_WORDS,), dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load_library().odh_lds_probe_verify(code, table.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    errors = h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF
+    xcd_blocks = h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD]
+    return {
+        "ok": errors == 0 and sum(xcd_blocks) == ODH_LDS_BLOCKS, "errors": errors, "blocks": sum(xcd_blocks),
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": xcd_blocks, "ms": e0.elapsed_time(e1),
+        "cus": sum(bin(w & 0xFFFFFFFF).count("1") for w in h[ODH_NCOUNT:]),
+    }
+
+
+def lds_probe(device: int, check) -> dict:
+    """One LDS probe of a GPU: the key table, then the fused check.  The dict of :func:`lds_verify`."""
+    import torch
+
+    code = _lds_check(check)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        table = torch.empty((ODH_LDS_TABLE,), dtype=torch.uint8, device=dev)
+        lds_fill(code, table)
+        return lds_verify(code, table)
+
+
+def lds_tr_read(check, image, lane_addr, raw: bool = False):
+    """One wave, one transposing LDS read (``tr16``, ``tr8``, ``tr4``, ``tr6``): ``image`` (uint8 on a GPU, a
+    multiple of 4 and at most 65536 bytes) is copied to LDS, lane ``l`` reads at byte address ``lane_addr[l]``
+    (64 of them).  Returns uint8 ``[64, 8]`` (``tr6``: ``[64, 12]``), a lane's result bytes in register order.
+    Addresses out of range or misaligned for the instruction raise ``ValueError`` before anything is launched;
+    ``raw`` leaves the alignment unchecked (what the instruction then returns was measured with it)."""
+    import torch
+
+    code = _lds_check(check)
+    if not ODH_LDS_TR16 <= code <= ODH_LDS_TR6:
+        raise ValueError("lds_tr_read takes one of the transposing reads: tr16, tr8, tr4, tr6")
+    if image.dtype != torch.uint8 or image.dim() != 1 or not image.is_cuda or not image.is_contiguous() \
+            or not 0 < image.numel() <= 65536 or image.numel() % 4 or image.data_ptr() % 4:
+        raise ValueError("image must be a contiguous, 4-byte aligned uint8 vector of at most 65536 bytes on a GPU")
+    addr = [int(a) for a in lane_addr]
+    width = 12 if code == ODH_LDS_TR6 else 8
+    align = 16 if code == ODH_LDS_TR6 else 8
+    if len(addr) != 64:
+        raise ValueError("lane_addr holds one address per lane: 64")
+    for a in addr:
+        if a < 0 or a + width > image.numel() or (not raw and a % align):
+            raise ValueError(f"lane address {a} is out of range or not {align}-byte aligned")
+    out = torch.zeros((64, width), dtype=torch.uint8, device=image.device)
+    host = (ctypes.c_uint32 * 64)(*addr)
+    _check(load_library().odh_lds_tr_read(code + (ODH_LDS_TR_RAW if raw else 0), image.data_ptr(), image.numel(),
+                                          ctypes.cast(host, ctypes.c_void_p), out.data_ptr(),
+                                          _stream_ptr(image.device)))
+    return out
+
+
+def lds_xlane(op, arg: int, values):
+    """One wave, one lane exchange of ``values`` (int32 or uint32-as-int32 ``[64]`` on a GPU; the two swaps:
+    ``[128]``, lane ``l``'s second register at ``64 + l``).  ``op`` is a name of :data:`LDS_XLANE_OPS` or its
+    number, ``arg`` its selector (``0 <= arg < LDS_XLANE_ARGS[op]``).  Returns the values after the exchange."""
+    import torch
+
+    name = op if isinstance(op, str) else {v: k for k, v in LDS_XLANE_OPS.items()}.get(op)
+    if name not in LDS_XLANE_OPS:
+        raise ValueError(f"op must be one of {sorted(LDS_XLANE_OPS)}; got {op!r}")
+    if not 0 <= arg < LDS_XLANE_ARGS[name]:
+        raise ValueError(f"{name} takes selectors 0 .. {LDS_XLANE_ARGS[name] - 1}; got {arg}")
+    n = 128 if name.endswith("_swap") else 64
+    if values.dtype != torch.int32 or tuple(values.shape) != (n,) or not values.is_cuda or not values.is_contiguous():
+        raise ValueError(f"values must be a contiguous int32 [{n}] tensor on a GPU")
+    out = torch.empty_like(values)
+    _check(load_library().odh_lds_xlane(LDS_XLANE_OPS[name], arg, values.data_ptr(), out.data_ptr(),
+                                        _stream_ptr(values.device)))
+    return out
+
+
+def transpose_codes(fmt, x):
+    """The transpose of a tensor of packed codes, on the GPU with the transposing LDS reads
+    (``ds_read_b64_tr_b16`` / ``_b8`` / ``_b4``, ``ds_read_b96_tr_b6``).  ``fmt``: ``bf16`` or ``f16`` (``x``
+    ``[R, C]`` of that dtype), or ``fp8``, ``bf8``, ``fp4``, ``fp6``, ``bf6``: ``x`` uint8 ``[R, row bytes]`` in the
+    layout :func:`mx_gemm` reads (a byte per element, two nibbles per byte with the even index low, or element
+    ``k`` in bits ``[6k, 6k + 6)`` of the row), the logical column count following from the row bytes.  Returns
+    the ``[C, R]`` codes in the same packing, bit for bit.  R and C are multiples of 128, ``x`` is contiguous and
+    16-byte aligned; anything else raises ``ValueError`` before launch."""
+    import torch
+
+    if fmt not in TRANSPOSE_FORMATS:
+        raise ValueError(f"format must be one of {sorted(TRANSPOSE_FORMATS)}; got {fmt!r}")
+    code, bits = TRANSPOSE_FORMATS[fmt]
+    want = {"bf16": torch.bfloat16, "f16": torch.float16}.get(fmt, torch.uint8)
+    if x.dtype != want:
+        raise ValueError(f"{fmt} codes are {want} tensors; got {x.dtype}")
+    if x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x must be a contiguous 2-D tensor on a GPU")
+    rows, row_bytes = x.shape[0], x.shape[1] * x.element_size()
+    if row_bytes * 8 % bits:
+        raise ValueError(f"a row of {row_bytes} bytes is no whole number of {bits}-bit elements")
+    cols = row_bytes * 8 // bits
+    if rows < 128 or cols < 128 or rows % 128 or cols % 128:
+        raise ValueError(f"rows and columns must be positive multiples of 128; got {rows} x {cols}")
+    if x.data_ptr() % 16:
+        raise ValueError("x must be 16-byte aligned")
+    out = torch.empty((cols, rows * bits // 8 // x.element_size()), dtype=x.dtype, device=x.device)
+    _check(load_library().odh_transpose_codes(code, x.data_ptr(), out.data_ptr(), rows, cols, _stream_ptr(x.device)))
+    return out
+
+
+def mx_transpose(fmt, b, sb):
+    """``(bt, sbt)`` as :func:`mx_gemm` takes them, from B held as ``[K, N]``: ``b`` the packed codes ``[K, row
+    bytes of N elements]`` and ``sb`` its E8M0 scales ``[K/32, N]`` (one per 32 elements along K).  Both go
+    through :func:`transpose_codes`, the scales as bytes; where K/32 is no multiple of 128 the scale rows are
+    padded with zeros up to one and the padding is cut off the result."""
+    import torch
+
+    code = _mx_format(fmt)
+    name = {v: k for k, v in MX_ALL_FORMATS.items()}[code]
+    bt = transpose_codes(name, b)
+    n, k = bt.shape[0], b.shape[0]
+    if sb.dtype != torch.uint8 or sb.dim() != 2 or tuple(sb.shape) != (k // 32, n) or sb.device != b.device:
+        raise ValueError(f"scales must be a uint8 [{k // 32},{n}] tensor on b's GPU")
+    pad = -(k // 32) % 128
+    if pad or not sb.is_contiguous() or sb.data_ptr() % 16:
+        sb = torch.cat([sb, torch.zeros((pad, n), dtype=torch.uint8, device=sb.device)])
+    sbt = transpose_codes("fp8", sb)
+    return bt, sbt[:, :k // 32].contiguous() if pad else sbt
 
 
 class GpuProbe:
