@@ -189,7 +189,8 @@ int odh_lds_tr_read(int check, const void* image, unsigned bytes, const uint32_t
                     hipStream_t stream);
 int odh_lds_xlane(int op, int arg, const uint32_t* in, uint32_t* out, hipStream_t stream);
 int odh_transpose_codes(int fmt, const void* src, void* dst, long R, long C, hipStream_t stream);
-// counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device
+// counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device;
+// *out: the handle, NULL after every failure
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out);
 int odh_probe_graph_launch(void* handle, hipStream_t stream);

@@ -1030,8 +1030,8 @@ static void probe_graph_free(ProbeGraph* g) {
 // ts_begin / ts_end pairs); host: the same size, pinned; seed: one u32 on the device
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,
                            void* hbm, size_t hbm_bytes, uint32_t* seed, int* host, int serial, void** out) {
+  if (out) *out = nullptr;  // whatever the outcome, the caller holds no stale handle
   if (!out || !gemm256_ok(M, N, K) || hbm_bytes < 16) return (int)hipErrorInvalidValue;
-  *out = nullptr;
   ProbeGraph* g = new ProbeGraph();
   hipError_t e = hipStreamCreateWithFlags(&g->s0, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->s1, hipStreamNonBlocking);

@@ -35,7 +35,9 @@
   (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
   layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
   (``odh-gpu-probe --cvt``); :func:`cvt_family` is that check's family of inputs and expected codes.
-* :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs.
+* :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs; a link is
+  :func:`link_check` of two probes, against :attr:`GpuProbe.pattern_seed` (the seed of the pattern the source's
+  buffer holds, whichever path wrote it), and two probes on one GPU make a link too.
 * The shipped start-up probe is none of these: it is the torch-free ``odh-gpu-probe`` init
   container (``csrc/probe_cli.cpp``, :mod:`.probe_main`), which launches the same kernels
   from plain hipMalloc'd buffers, serially on the null stream.
@@ -1228,6 +1230,9 @@ class GpuProbe:
         self._graph_error: Optional[str] = None
         self.runs = 0
         self.seed = 0x9E3779B9
+        # the pattern in ``hbm``: None (none yet, or a run that failed part-way), "graph" (the seed is in
+        # ``seed_dev``: the replay advanced it on the device) or the seed itself (the eager launches)
+        self._pattern = None
         # one probe in flight per GPU: runs share the counters, events and pinned host buffer
         # (two pods probing the same device — ranks sharing a GPU in a rehearsal — take turns)
         self._lock = threading.Lock()
@@ -1272,8 +1277,18 @@ class GpuProbe:
     def close(self) -> None:
         with self._lock:
             if self._graph is not None:
+                self._pattern = self.pattern_seed  # the next capture starts a fresh ``seed_dev``
                 load_library().odh_probe_graph_destroy(self._graph)
                 self._graph = None
+
+    @property
+    def pattern_seed(self) -> Optional[int]:
+        """The seed of the pattern ``hbm`` holds now, whichever path wrote it: the host-side ``seed`` of the
+        eager launches, or the device-side one a graph replay advanced (read back here, not per run).
+        ``None`` before the first run.  Not locked: a caller racing :meth:`run` holds ``_lock``."""
+        if self._pattern == "graph":
+            return int(self.seed_dev.item()) & 0xFFFFFFFF
+        return self._pattern
 
     def _span_ms(self, h: List[int], i: int) -> float:
         begin = ~_u64(h, i) & 0xFFFFFFFFFFFFFFFF
@@ -1297,8 +1312,10 @@ class GpuProbe:
 
     def _run_graph(self, graph) -> dict:
         t0 = time.perf_counter()
+        self._pattern = None
         self._launch_graph(graph)
         self.ev[4].synchronize()
+        self._pattern = "graph"
         return self._graph_result(t0)
 
     def _run(self) -> dict:
@@ -1312,6 +1329,7 @@ class GpuProbe:
             xcd_blocks, err_xcd, gemm_err, hbm_err = (cnt.data_ptr() + 4 * slot for slot in (
                 ODH_SLOT_XCD_BLOCKS, ODH_SLOT_ERR_XCD, ODH_SLOT_GEMM_ERR, ODH_SLOT_HBM_ERR))
             self.seed = (self.seed * 1664525 + 1013904223) & 0xFFFFFFFF
+            self._pattern = None
             sg.wait_stream(torch.cuda.current_stream(self.device))  # caller's writes to a / bt / hbm
             with torch.cuda.stream(sg):
                 cnt.zero_()
@@ -1348,6 +1366,7 @@ class GpuProbe:
                 self.host.copy_(cnt, non_blocking=True)
                 self.ev[4].record(sg)
             self.ev[4].synchronize()
+        self._pattern = self.seed
         h = self.host.tolist()
         return self._result(h, self.ev[0].elapsed_time(self.ev[1]), self.ev[2].elapsed_time(self.ev[3]),
                             self.ev[0].elapsed_time(self.ev[4]), t0, graph=False)
@@ -1397,45 +1416,62 @@ def ring_pairs(devices: Sequence[int]) -> List[tuple]:
     return [(ds[(n + 1) % len(ds)], ds[n]) for n in range(len(ds))]
 
 
+def link_check(pr: GpuProbe, ps: GpuProbe, nbytes: int = XGMI_CHECK_BYTES) -> dict:
+    """One link: the GPU of probe ``pr`` reads the first ``nbytes`` of the HBM buffer of probe ``ps`` and
+    verifies every word against the pattern ``ps`` wrote last (:attr:`GpuProbe.pattern_seed`).  Two probes
+    on one device are a link like any other, without the peer mapping.  Whatever goes wrong, a source
+    that has not run yet included, is the link's ``error``: no count, and not ok."""
+    import torch
+
+    reader, source = pr.device.index, ps.device.index
+    r = {"reader": reader, "source": source, "ok": False}
+    try:
+        if pr is ps:
+            raise ValueError("a link has two probes")
+        n = min(nbytes, ps.hbm_bytes) & ~15
+        first, second = sorted((pr, ps), key=lambda p: (p.device.index, id(p)))  # one order for every caller
+        with first._lock, second._lock:
+            seed = ps.pattern_seed
+            if seed is None:
+                raise RuntimeError(f"the probe of GPU {source} has written no pattern yet")
+            _check(load_library().odh_peer_enable(reader, source))
+            dev = pr.device
+            with torch.cuda.device(dev):
+                err = torch.zeros((2,), dtype=torch.int32, device=dev)
+                s = pr.streams[0]
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.wait_stream(torch.cuda.current_stream(dev))
+                torch.cuda.current_stream(ps.device).synchronize()  # source pattern is in HBM
+                ev0.record(s)
+                _check(load_library().odh_hbm_check(ps.hbm.data_ptr(), n, seed, err.data_ptr(), s.cuda_stream))
+                ev1.record(s)
+                ev1.synchronize()
+                e = err.cpu().tolist()
+            ms = ev0.elapsed_time(ev1)
+        errors = _u64(e, 0)
+        r.update(ok=errors == 0, errors=errors, bytes=n, ms=ms, gbps=n / (ms * 1e-3) / 1e9 if ms > 0 else 0.0)
+    except Exception as ex:  # a link that cannot be checked fails the pod, not the agent
+        r["error"] = repr(ex)
+    return r
+
+
 def xgmi_ring_check(devices: Sequence[int], nbytes: int = XGMI_CHECK_BYTES) -> List[dict]:
     """Peer-read check of a multi-GPU pod's xGMI links.
 
     Each GPU's probe has just written its seeded pattern into its HBM buffer; GPU
     ``reader`` now streams the first ``nbytes`` of GPU ``source``'s buffer over xGMI and
-    verifies every word (``odh_hbm_check`` with a peer pointer).  One link failing fails
-    the pod, like an XCD failing the GEMM check.  The reference has no equivalent: a
+    verifies every word (:func:`link_check`: ``odh_hbm_check`` with a peer pointer).  One link failing
+    fails the pod, like an XCD failing the GEMM check.  The reference has no equivalent: a
     multi-GPU notebook there starts on GPUs whose interconnect nobody has looked at.
     """
-    import torch
-
-    lib = load_library()
     out = []
     for reader, source in ring_pairs(devices):
-        r = {"reader": reader, "source": source, "ok": False}
         try:
             pr, ps = get_probe(reader), get_probe(source)
-            n = min(nbytes, ps.hbm_bytes) & ~15
-            first, second = sorted((pr, ps), key=lambda p: p.device.index)
-            with first._lock, second._lock:
-                _check(lib.odh_peer_enable(reader, source))
-                dev = pr.device
-                with torch.cuda.device(dev):
-                    err = torch.zeros((2,), dtype=torch.int32, device=dev)
-                    s = pr.streams[0]
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s.wait_stream(torch.cuda.current_stream(dev))
-                    torch.cuda.current_stream(ps.device).synchronize()  # source pattern is in HBM
-                    ev0.record(s)
-                    _check(lib.odh_hbm_check(ps.hbm.data_ptr(), n, ps.seed, err.data_ptr(), s.cuda_stream))
-                    ev1.record(s)
-                    ev1.synchronize()
-                    e = err.cpu().tolist()
-                ms = ev0.elapsed_time(ev1)
-            errors = _u64(e, 0)
-            r.update(ok=errors == 0, errors=errors, bytes=n, ms=ms, gbps=n / (ms * 1e-3) / 1e9 if ms > 0 else 0.0)
-        except Exception as ex:  # a link that cannot be checked fails the pod, not the agent
-            r["error"] = repr(ex)
-        out.append(r)
+        except Exception as ex:  # a probe that cannot be built fails its links
+            out.append({"reader": reader, "source": source, "ok": False, "error": repr(ex)})
+            continue
+        out.append(link_check(pr, ps, nbytes))
     return out
 
 

@@ -94,6 +94,73 @@ def fused_tile_id(tm, tn, tiles_m, tiles_n, gm=1):
     return tm * tiles_n + tn
 
 
+def tile128_id(tm, tn, tiles_n):
+    """The tile id of output tile ``(tm, tn)`` in the 128² store kernel and its check kernel: row-major."""
+    return tm * tiles_n + tn
+
+
+def line_errors(other, c, tile):
+    """One operand element at k = ``c`` off by a non-zero amount makes its line of C (a row for an
+    element of A, a column for one of Bt) wrong exactly where the other operand ``other[:, c]`` is not 0.
+    Returns the count and the counts per ``tile`` elements along the line."""
+    bad = other[:, c] != 0
+    return int(bad.sum()), bad.reshape(-1, tile).sum(axis=1).tolist()
+
+
+def errors_by_xcd(per_tile, xcds):
+    """``per_tile[t]`` mismatches in a tile that ran on XCD ``xcds[t]``, summed per XCD."""
+    out = [0] * N_XCD
+    for count, xcd in zip(per_tile, xcds):
+        out[int(xcd)] += int(count)
+    return out
+
+
+# ------------------------------------------------------------------ the resident probe's harness
+
+
+GRAPH_SEED0 = 0x1E3779B9  # the device-side seed before the first replay
+EAGER_SEED0 = 0x9E3779B9  # the host-side seed before the first eager run
+
+
+def lcg_sequence(seed, n):
+    """The seeds of runs 1 .. n from the start value ``seed``."""
+    out = []
+    for _ in range(n):
+        seed = lcg(seed)
+        out.append(seed)
+    return out
+
+
+def u64(h, i):
+    """The u64 in the i32 slots ``i`` and ``i + 1`` of a counter block."""
+    return (int(h[i]) & 0xFFFFFFFF) | ((int(h[i + 1]) & 0xFFFFFFFF) << 32)
+
+
+def graph_span(h, slot):
+    """``(begin, end)`` in ticks of a span of the graph layout: ``~begin`` in slots ``slot`` and
+    ``slot + 1`` (so that a zeroed slot works with an atomic max), ``end`` in the next two."""
+    return ~u64(h, slot) & 0xFFFFFFFFFFFFFFFF, u64(h, slot + 2)
+
+
+def sweep_workgroups(n16):
+    """Workgroups of the pattern sweep over ``n16`` elements: one per 1024, at most 4096."""
+    return max(1, min(4096, -(-n16 // 1024)))
+
+
+def link_flips(words, inside, seed, count=200):
+    """Seeded places to corrupt in a buffer of ``words`` words of which a reader checks the first
+    ``inside``: the first and the last word of the buffer, both words at the boundary, and ``count``
+    random ones on either side of it.  Returns sorted positions and a non-zero int32 to XOR into each."""
+    rng = np.random.default_rng(seed)
+    pos = {0, words - 1, inside - 1}
+    pos.update(rng.choice(inside, size=min(count, inside), replace=False).tolist())
+    if inside < words:
+        pos.add(inside)
+        pos.update((inside + rng.choice(words - inside, size=min(count, words - inside), replace=False)).tolist())
+    pos = np.array(sorted(pos), dtype=np.int64)
+    return pos, rng.integers(1, 1 << 31, size=pos.size, dtype=np.int64).astype(np.int32)
+
+
 # ------------------------------------------------------------------ f16: value against value
 
 

@@ -89,6 +89,34 @@ def test_fused_tile_id_is_a_bijection():
         assert ids == list(range(tiles_m * tiles_n))
 
 
+def test_graph_and_eager_seeds_never_name_the_same_pattern():
+    """The two start values differ in bit 31 alone and the LCG's multiplier is odd, so the orbits differ in
+    bit 31 at every step; ``mix32`` is a bijection, so every word of the two patterns differs: a link checked
+    against the wrong one of the two seeds counts every word."""
+    assert ref.GRAPH_SEED0 ^ ref.EAGER_SEED0 == 1 << 31
+    g, e = ref.lcg_sequence(ref.GRAPH_SEED0, 64), ref.lcg_sequence(ref.EAGER_SEED0, 64)
+    assert g[0] == ref.lcg(ref.GRAPH_SEED0) and g[1] == ref.lcg(g[0]) and len(set(g)) == 64
+    assert all(a ^ b == 1 << 31 for a, b in zip(g, e))
+    assert (ref.pattern_words(4099, g[2]) != ref.pattern_words(4099, e[2])).all()
+
+
+def test_harness_helpers():
+    h = [0] * 32
+    h[20], h[21] = -6, -1  # ~5 as two i32
+    h[22], h[23] = 9, 1
+    assert ref.graph_span(h, 20) == (5, (1 << 32) + 9) and ref.u64(h, 22) == (1 << 32) + 9
+    assert ref.graph_span(h, 24) == (0xFFFFFFFFFFFFFFFF, 0)  # a span nothing stamped
+    assert [ref.sweep_workgroups(n) for n in (1, 1024, 1025, 4096 * 1024, 1 << 30)] == [1, 1, 2, 4096, 4096]
+    pos, xor = ref.link_flips(1000, 256, seed=3)
+    assert len(set(pos.tolist())) == len(pos) and {0, 255, 256, 999} <= set(pos.tolist())
+    assert pos.min() >= 0 and pos.max() < 1000 and (xor != 0).all() and xor.dtype == np.int32
+    _, bt = ref.probe_operands(1, 512, 64)
+    total, per_tile = ref.line_errors(bt, 37, 256)
+    assert total == sum(per_tile) == int((bt[:, 37] != 0).sum()) and len(per_tile) == 2
+    assert ref.errors_by_xcd([3, 4, 5], [7, 0, 7]) == [4, 0, 0, 0, 0, 0, 0, 8]
+    assert ref.tile128_id(1, 2, 3) == 5
+
+
 def test_gpu_probe_refuses_a_vacuous_shape():
     with pytest.raises(ValueError, match="35"):
         gpu.GpuProbe(0, 256, 256, 2240)
