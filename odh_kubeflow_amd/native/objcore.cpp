@@ -17,6 +17,10 @@
 //                          subtrees of ``old`` the new document leaves unchanged
 //   loads_event(line, lookup) one watch event line -> (type, object), the object decoded
 //                          against lookup(namespace, name) — the informer's cached version
+//   WatchStore             an informer's objects, fed with the raw bytes of its watch response:
+//                          framing (watch_feed.hpp), decoding against the stored versions and
+//                          the store itself in one call per arrival
+//   canonical(o)           json.dumps(o, sort_keys=True, separators=(",", ":")) as bytes
 //
 // Why share: a watch MODIFIED event carries the whole object again, while a status write
 // changes a handful of fields.  Decoding against the cached version allocates only the
@@ -26,6 +30,7 @@
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -36,6 +41,8 @@
 #include <unordered_map>
 #include <utility>
 #include <vector>
+
+#include "watch_feed.hpp"
 
 namespace {
 
@@ -235,6 +242,9 @@ struct Parser {
   // owned references of the objects and arrays being built, innermost last: a container's
   // members are collected here (one allocation for the whole document, not one per dict)
   std::vector<PyObject*> stack;
+  // WatchStore: the event object's metadata.managedFields is skipped, never built
+  bool strip_mf = false;
+  bool meta_next = false;  // the object about to be parsed is that metadata
 };
 
 // a container's run of owned references on ps.stack, released (and popped) on every exit
@@ -506,6 +516,7 @@ PyObject* number_value(Parser& ps, PyObject* old) {
 }
 
 PyObject* value(Parser& ps, PyObject* old, int depth);
+bool skip_value(Parser& ps, int depth);
 
 PyObject* object_value(Parser& ps, PyObject* old, int depth) {
   // ps.p just past '{'.  With an old dict the members are collected first: an unchanged
@@ -517,6 +528,8 @@ PyObject* object_value(Parser& ps, PyObject* old, int depth) {
   // the i-th key is usually the old i-th one (no hashing, no lookup)
   Py_ssize_t pos = 0;
   bool in_step = od != nullptr;
+  const bool strip_here = ps.meta_next;  // this object is the event object's metadata
+  ps.meta_next = false;
   ws(ps);
   if (ps.p < ps.end && *ps.p == '}') {
     ++ps.p;
@@ -529,6 +542,24 @@ PyObject* object_value(Parser& ps, PyObject* old, int depth) {
       Py_ssize_t kn;
       bool kascii;
       if (!scan_string(ps, &ks, &kn, &kascii)) return nullptr;
+      if (strip_here && kn == 13 && std::memcmp(ks, "managedFields", 13) == 0) {
+        // as if the member were not there: the stored metadata has none either
+        ws(ps);
+        if (ps.p >= ps.end || *ps.p != ':') return fail(ps, "expected ':'");
+        ++ps.p;
+        if (!skip_value(ps, depth + 1)) return fail(ps, "bad managedFields");
+        ws(ps);
+        if (ps.p < ps.end && *ps.p == ',') {
+          ++ps.p;
+          continue;
+        }
+        if (ps.p < ps.end && *ps.p == '}') {
+          ++ps.p;
+          break;
+        }
+        return fail(ps, "expected ',' or '}'");
+      }
+      const bool meta = ps.strip_mf && depth == 0 && kn == 8 && std::memcmp(ks, "metadata", 8) == 0;
       PyObject* key = nullptr;
       PyObject* ov = nullptr;
       if (in_step) {
@@ -552,7 +583,9 @@ PyObject* object_value(Parser& ps, PyObject* old, int depth) {
       ws(ps);
       if (ps.p >= ps.end || *ps.p != ':') return fail(ps, "expected ':'");
       ++ps.p;
+      ps.meta_next = meta;
       PyObject* v = value(ps, ov, depth + 1);
+      ps.meta_next = false;
       if (!v) return nullptr;
       ps.stack.push_back(v);
       if (v != ov) same = false;
@@ -647,11 +680,14 @@ PyObject* value(Parser& ps, PyObject* old, int depth) {
     PyErr_SetString(PyExc_RecursionError, "JSON too deep");
     return nullptr;
   }
+  const bool meta = ps.meta_next;  // holds for an object only, and for this one alone
+  ps.meta_next = false;
   ws(ps);
   if (ps.p >= ps.end) return fail(ps, "unexpected end");
   char c = *ps.p;
   if (c == '{') {
     ++ps.p;
+    ps.meta_next = meta;
     return object_value(ps, old, depth);
   }
   if (c == '[') {
@@ -835,19 +871,20 @@ PyObject* py_loads_shared(PyObject*, PyObject* args) {
   return out;
 }
 
-// loads_event(line, lookup) -> (type, object): lookup(namespace, name) gives the cached
-// version of the event's object (or None) to share unchanged subtrees with
-PyObject* py_loads_event(PyObject*, PyObject* args) {
-  PyObject *data, *lookup = Py_None;
-  if (!PyArg_ParseTuple(args, "O|O", &data, &lookup)) return nullptr;
-  Parser ps;
-  if (!init_parser(data, &ps)) return nullptr;
+// One watch event line at ps.p -> *type (None when absent) and *obj (new references).
+// lookup(ns, name, &old) -> bool gives the stored version of the event's object to share
+// unchanged subtrees with (a new reference, or null); false: a Python error is set.
+template <class Lookup>
+bool decode_event(Parser& ps, Lookup&& lookup, PyObject** type_out, PyObject** obj_out) {
   ws(ps);
-  if (ps.p >= ps.end || *ps.p != '{') return fail(ps, "an event is an object");
+  if (ps.p >= ps.end || *ps.p != '{') {
+    fail(ps, "an event is an object");
+    return false;
+  }
   ++ps.p;
   PyObject* type = nullptr;
   PyObject* obj = nullptr;
-  PyObject* ret = nullptr;
+  bool ok = false;
   ws(ps);
   if (ps.p < ps.end && *ps.p == '}') {
     ++ps.p;
@@ -873,17 +910,9 @@ PyObject* py_loads_event(PyObject*, PyObject* args) {
       ++ps.p;
       if (is_obj) {
         PyObject* old = nullptr;
-        if (lookup != Py_None) {
-          std::string ns, name;
-          peek_key(ps, &ns, &name);
-          if (!name.empty()) {
-            PyObject* r = PyObject_CallFunction(lookup, "s#s#", ns.data(), static_cast<Py_ssize_t>(ns.size()),
-                                                name.data(), static_cast<Py_ssize_t>(name.size()));
-            if (!r) goto done;
-            if (r != Py_None) old = r;
-            else Py_DECREF(r);
-          }
-        }
+        std::string ns, name;
+        peek_key(ps, &ns, &name);
+        if (!name.empty() && !lookup(ns, name, &old)) goto done;
         Py_XDECREF(obj);
         obj = value(ps, old, 0);
         Py_XDECREF(old);
@@ -918,10 +947,43 @@ PyObject* py_loads_event(PyObject*, PyObject* args) {
   }
   if (!obj) obj = PyDict_New();
   if (!obj) goto done;
-  ret = PyTuple_Pack(2, type ? type : Py_None, obj);
+  if (!type) {
+    type = Py_None;
+    Py_INCREF(type);
+  }
+  ok = true;
 done:
-  Py_XDECREF(type);
-  Py_XDECREF(obj);
+  if (!ok) {
+    Py_XDECREF(type);
+    Py_XDECREF(obj);
+    return false;
+  }
+  *type_out = type;
+  *obj_out = obj;
+  return true;
+}
+
+// loads_event(line, lookup) -> (type, object): lookup(namespace, name) gives the cached
+// version of the event's object (or None) to share unchanged subtrees with
+PyObject* py_loads_event(PyObject*, PyObject* args) {
+  PyObject *data, *lookup = Py_None;
+  if (!PyArg_ParseTuple(args, "O|O", &data, &lookup)) return nullptr;
+  Parser ps;
+  if (!init_parser(data, &ps)) return nullptr;
+  PyObject *type, *obj;
+  auto find = [lookup](const std::string& ns, const std::string& name, PyObject** old) {
+    if (lookup == Py_None) return true;
+    PyObject* r = PyObject_CallFunction(lookup, "s#s#", ns.data(), static_cast<Py_ssize_t>(ns.size()),
+                                        name.data(), static_cast<Py_ssize_t>(name.size()));
+    if (!r) return false;
+    if (r != Py_None) *old = r;
+    else Py_DECREF(r);
+    return true;
+  };
+  if (!decode_event(ps, find, &type, &obj)) return nullptr;
+  PyObject* ret = PyTuple_Pack(2, type, obj);
+  Py_DECREF(type);
+  Py_DECREF(obj);
   return ret;
 }
 
@@ -1060,7 +1122,403 @@ PyObject* py_dumps(PyObject*, PyObject* o) {
   return PyBytes_FromStringAndSize(out.data(), static_cast<Py_ssize_t>(out.size()));
 }
 
+// canonical(obj) -> bytes: json.dumps(obj, sort_keys=True, separators=(",", ":")) byte for byte
+// (object keys in code-point order, everything outside printable ASCII as \uXXXX): a content
+// key for caches.  Anything but a plain JSON tree raises TypeError; the caller uses json.dumps.
+
+void canon_string(std::string& out, PyObject* u) {
+  const int kind = PyUnicode_KIND(u);
+  const void* data = PyUnicode_DATA(u);
+  const Py_ssize_t n = PyUnicode_GET_LENGTH(u);
+  static const char* hex = "0123456789abcdef";
+  auto u4 = [&out](uint32_t c) {
+    const char b[6] = {'\\', 'u', hex[(c >> 12) & 15], hex[(c >> 8) & 15], hex[(c >> 4) & 15], hex[c & 15]};
+    out.append(b, 6);
+  };
+  out.push_back('"');
+  for (Py_ssize_t i = 0; i < n; ++i) {
+    const uint32_t c = PyUnicode_READ(kind, data, i);
+    if (c >= 0x20 && c < 0x7f && c != '"' && c != '\\') {
+      out.push_back(static_cast<char>(c));
+      continue;
+    }
+    switch (c) {
+      case '"': out.append("\\\""); break;
+      case '\\': out.append("\\\\"); break;
+      case '\n': out.append("\\n"); break;
+      case '\r': out.append("\\r"); break;
+      case '\t': out.append("\\t"); break;
+      case '\b': out.append("\\b"); break;
+      case '\f': out.append("\\f"); break;
+      default:
+        if (c >= 0x10000) {
+          const uint32_t v = c - 0x10000;
+          u4(0xD800 | ((v >> 10) & 0x3FF));
+          u4(0xDC00 | (v & 0x3FF));
+        } else {
+          u4(c);
+        }
+    }
+  }
+  out.push_back('"');
+}
+
+bool canon_value(std::string& out, PyObject* o, int depth) {
+  if (depth > 512) {
+    PyErr_SetString(PyExc_ValueError, "too deep");
+    return false;
+  }
+  if (PyUnicode_CheckExact(o)) {
+    canon_string(out, o);
+    return true;
+  }
+  if (PyDict_CheckExact(o)) {
+    std::vector<std::pair<PyObject*, PyObject*>> members;
+    members.reserve(static_cast<size_t>(PyDict_GET_SIZE(o)));
+    Py_ssize_t pos = 0;
+    PyObject *k, *v;
+    while (PyDict_Next(o, &pos, &k, &v)) {
+      if (!PyUnicode_CheckExact(k)) {  // json converts or rejects such keys: its business
+        PyErr_SetString(PyExc_TypeError, "non-str key");
+        return false;
+      }
+      members.emplace_back(k, v);
+    }
+    std::sort(members.begin(), members.end(),
+              [](const auto& a, const auto& b) { return PyUnicode_Compare(a.first, b.first) < 0; });
+    out.push_back('{');
+    bool first = true;
+    for (const auto& kv : members) {
+      if (!first) out.push_back(',');
+      first = false;
+      canon_string(out, kv.first);
+      out.push_back(':');
+      if (!canon_value(out, kv.second, depth + 1)) return false;
+    }
+    out.push_back('}');
+    return true;
+  }
+  if (PyList_CheckExact(o) || PyTuple_CheckExact(o)) {
+    const bool list = PyList_CheckExact(o);
+    const Py_ssize_t n = list ? PyList_GET_SIZE(o) : PyTuple_GET_SIZE(o);
+    out.push_back('[');
+    for (Py_ssize_t i = 0; i < n; ++i) {
+      if (i) out.push_back(',');
+      if (!canon_value(out, list ? PyList_GET_ITEM(o, i) : PyTuple_GET_ITEM(o, i), depth + 1)) return false;
+    }
+    out.push_back(']');
+    return true;
+  }
+  if (PyUnicode_Check(o) || PyDict_Check(o) || PyList_Check(o)) {  // subclasses: json's business
+    PyErr_SetString(PyExc_TypeError, "not a plain JSON tree");
+    return false;
+  }
+  return enc_value(out, o, depth);  // None, bool, int, float; TypeError for anything else
+}
+
+PyObject* py_canonical(PyObject*, PyObject* o) {
+  std::string out;
+  out.reserve(1024);
+  if (!canon_value(out, o, 0)) {
+    if (!PyErr_Occurred()) PyErr_SetString(PyExc_TypeError, "not a JSON tree");
+    return nullptr;
+  }
+  return PyBytes_FromStringAndSize(out.data(), static_cast<Py_ssize_t>(out.size()));
+}
+
+// ------------------------------------------------------------------ watch store
+// WatchStore(api_version, kind, namespaced=True): an informer's objects, fed with the bytes
+// of its watch response.
+//
+//   items                the (namespace, name) -> object dict, a plain dict the informer reads
+//   begin(want)          a response body starts: -2 chunked, -3 until EOF, else its length
+//   feed(data, apply=True) -> [(type, new, old)]   the events the bytes complete, in order
+//   done                 the body has ended (terminal chunk and trailer, or its length)
+//   failed               None, or why this body cannot be read further
+//
+// feed() frames the bytes (watch_feed.hpp), decodes every event against the stored object of
+// its (namespace, name) — unchanged subtrees are the stored ones —, never builds
+// metadata.managedFields, sets apiVersion / kind when absent and, with ``apply``, stores the
+// object (or pops it, for DELETED) and hands back the one it replaced.  ``apply=False`` leaves
+// the dict alone (``old`` is None): the caller's policy decides, and writes ``items`` itself.
+// A BOOKMARK comes back as (type, object, None) and is not stored.  An ERROR event ends the
+// body: it comes back last, after the events before it.  A line the decoder declines (NaN
+// literals, anything json.loads might still take) comes back raw as (None, line, None).
+// Bytes that cannot be framed, or JSON nested deeper than 512, fail the body: feed() raises
+// ValueError — at once when no event precedes the fault in this call, else on the next call,
+// after the events before it were handed over (``failed`` is set either way).  Events handed
+// over are in the dict, events not handed over are not.
+
+struct WatchStore {
+  PyObject_HEAD
+  PyObject* items;
+  PyObject* api_version;
+  PyObject* kind;
+  bool namespaced;
+  watchfeed::Framer* framer;
+  std::string* failed;
+  Parser* ps;
+};
+
+PyObject* g_str_metadata = nullptr;
+PyObject* g_str_namespace = nullptr;
+PyObject* g_str_name = nullptr;
+PyObject* g_str_api_version = nullptr;
+PyObject* g_str_kind = nullptr;
+PyObject* g_str_empty = nullptr;
+
+void ws_dealloc(WatchStore* self) {
+  Py_XDECREF(self->items);
+  Py_XDECREF(self->api_version);
+  Py_XDECREF(self->kind);
+  delete self->framer;
+  delete self->failed;
+  delete self->ps;
+  PyTypeObject* type = Py_TYPE(self);
+  type->tp_free(reinterpret_cast<PyObject*>(self));
+  Py_DECREF(type);  // a heap type: every instance holds a reference to it
+}
+
+PyObject* ws_new(PyTypeObject* type, PyObject* args, PyObject* kw) {
+  static const char* names[] = {"api_version", "kind", "namespaced", nullptr};
+  PyObject *av, *kind;
+  int namespaced = 1;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "UU|p", const_cast<char**>(names), &av, &kind, &namespaced))
+    return nullptr;
+  WatchStore* self = reinterpret_cast<WatchStore*>(type->tp_alloc(type, 0));
+  if (!self) return nullptr;
+  self->framer = new watchfeed::Framer();
+  self->failed = new std::string();
+  self->ps = new Parser();
+  self->ps->strip_mf = true;
+  self->namespaced = namespaced != 0;
+  Py_INCREF(av);
+  self->api_version = av;
+  Py_INCREF(kind);
+  self->kind = kind;
+  self->items = PyDict_New();
+  if (!self->items) {
+    Py_DECREF(self);
+    return nullptr;
+  }
+  return reinterpret_cast<PyObject*>(self);
+}
+
+PyObject* ws_begin(WatchStore* self, PyObject* arg) {
+  const long long want = PyLong_AsLongLong(arg);
+  if (want == -1 && PyErr_Occurred()) return nullptr;
+  try {
+    self->framer->begin(want);
+  } catch (const watchfeed::FrameError& e) {
+    PyErr_SetString(PyExc_ValueError, e.what());
+    return nullptr;
+  }
+  self->failed->clear();
+  Py_RETURN_NONE;
+}
+
+// obj["metadata"][which], or "" (as models.meta.namespace / name read it); a new reference
+PyObject* meta_field(PyObject* obj, PyObject* which) {
+  PyObject* md = PyDict_GetItemWithError(obj, g_str_metadata);
+  PyObject* v = nullptr;
+  if (md && PyDict_Check(md)) v = PyDict_GetItemWithError(md, which);
+  if (!v) {
+    if (PyErr_Occurred()) return nullptr;
+    v = g_str_empty;
+  }
+  Py_INCREF(v);
+  return v;
+}
+
+enum LineResult { kLineOk, kLineStop, kLineFailed, kLineError };
+
+// one complete line into ``out``
+LineResult ws_line(WatchStore* self, const char* s, size_t n, bool apply, PyObject* out) {
+  Parser& ps = *self->ps;
+  ps.p = s;
+  ps.end = s + n;
+  ps.meta_next = false;
+  PyObject* type = nullptr;
+  PyObject* obj = nullptr;
+  auto find = [self](const std::string& ns, const std::string& name, PyObject** old) {
+    PyObject* k = Py_BuildValue("(s#s#)", self->namespaced ? ns.data() : "",
+                                self->namespaced ? static_cast<Py_ssize_t>(ns.size()) : Py_ssize_t{0}, name.data(),
+                                static_cast<Py_ssize_t>(name.size()));
+    if (!k) {  // not UTF-8: the line is declined below, json has the last word
+      PyErr_Clear();
+      return true;
+    }
+    PyObject* hit = PyDict_GetItemWithError(self->items, k);
+    Py_DECREF(k);
+    if (!hit && PyErr_Occurred()) return false;
+    Py_XINCREF(hit);
+    *old = hit;
+    return true;
+  };
+  PyObject* entry = nullptr;
+  if (!decode_event(ps, find, &type, &obj)) {
+    if (PyErr_ExceptionMatches(PyExc_RecursionError)) {
+      PyErr_Clear();
+      *self->failed = "invalid JSON: nested deeper than 512";
+      return kLineFailed;
+    }
+    if (!PyErr_ExceptionMatches(PyExc_ValueError)) return kLineError;
+    PyErr_Clear();
+  } else if (!PyUnicode_CheckExact(type) || !PyDict_CheckExact(obj)) {
+    Py_CLEAR(type);  // not the shape of an event: the caller's json path says what it is
+    Py_CLEAR(obj);
+  }
+  if (!type) {
+    PyObject* raw = PyBytes_FromStringAndSize(s, static_cast<Py_ssize_t>(n));
+    if (!raw) return kLineError;
+    entry = PyTuple_Pack(3, Py_None, raw, Py_None);
+    Py_DECREF(raw);
+    if (!entry || PyList_Append(out, entry) < 0) {
+      Py_XDECREF(entry);
+      return kLineError;
+    }
+    Py_DECREF(entry);
+    return kLineOk;
+  }
+  LineResult res = kLineOk;
+  PyObject* old = nullptr;  // a new reference
+  const bool is_error = PyUnicode_CompareWithASCIIString(type, "ERROR") == 0;
+  if (is_error) {
+    res = kLineStop;
+  } else if (PyUnicode_CompareWithASCIIString(type, "BOOKMARK") != 0) {
+    if (!PyDict_SetDefault(obj, g_str_api_version, self->api_version) ||
+        !PyDict_SetDefault(obj, g_str_kind, self->kind))
+      res = kLineError;
+    if (res == kLineOk && apply) {
+      PyObject* ns = meta_field(obj, g_str_namespace);
+      PyObject* name = ns ? meta_field(obj, g_str_name) : nullptr;
+      PyObject* k = name ? PyTuple_Pack(2, ns, name) : nullptr;
+      Py_XDECREF(ns);
+      Py_XDECREF(name);
+      if (!k) {
+        res = kLineError;
+      } else {
+        old = PyDict_GetItemWithError(self->items, k);
+        Py_XINCREF(old);
+        if (!old && PyErr_Occurred()) {
+          res = kLineError;
+        } else if (PyUnicode_CompareWithASCIIString(type, "DELETED") == 0) {
+          if (old && PyDict_DelItem(self->items, k) < 0) res = kLineError;
+        } else if (PyDict_SetItem(self->items, k, obj) < 0) {
+          res = kLineError;
+        }
+        Py_DECREF(k);
+      }
+    }
+  }
+  if (res != kLineError) {
+    entry = PyTuple_Pack(3, type, obj, old ? old : Py_None);
+    if (!entry || PyList_Append(out, entry) < 0) res = kLineError;
+    Py_XDECREF(entry);
+  }
+  Py_XDECREF(old);
+  Py_DECREF(type);
+  Py_DECREF(obj);
+  return res;
+}
+
+PyObject* ws_feed(WatchStore* self, PyObject* args, PyObject* kw) {
+  static const char* names[] = {"data", "apply", nullptr};
+  Py_buffer view;
+  int apply = 1;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "y*|p", const_cast<char**>(names), &view, &apply)) return nullptr;
+  if (!self->failed->empty()) {
+    PyBuffer_Release(&view);
+    PyErr_SetString(PyExc_ValueError, self->failed->c_str());
+    return nullptr;
+  }
+  PyObject* out = PyList_New(0);
+  if (!out) {
+    PyBuffer_Release(&view);
+    return nullptr;
+  }
+  bool error = false;
+  try {
+    self->framer->feed(static_cast<const char*>(view.buf), static_cast<size_t>(view.len),
+                       [&](const char* s, size_t n) {
+                         const LineResult r = ws_line(self, s, n, apply != 0, out);
+                         if (r == kLineError) error = true;
+                         return r == kLineOk;
+                       });
+  } catch (const watchfeed::FrameError& e) {
+    *self->failed = std::string("bad watch response body: ") + e.what();
+  }
+  PyBuffer_Release(&view);
+  self->ps->p = self->ps->end = nullptr;
+  if (error) {
+    Py_DECREF(out);
+    return nullptr;
+  }
+  if (!self->failed->empty() && PyList_GET_SIZE(out) == 0) {
+    Py_DECREF(out);
+    PyErr_SetString(PyExc_ValueError, self->failed->c_str());
+    return nullptr;
+  }
+  return out;
+}
+
+PyObject* ws_get_items(WatchStore* self, void*) {
+  Py_INCREF(self->items);
+  return self->items;
+}
+
+PyObject* ws_get_done(WatchStore* self, void*) { return PyBool_FromLong(self->framer->done()); }
+
+PyObject* ws_get_failed(WatchStore* self, void*) {
+  if (self->failed->empty()) Py_RETURN_NONE;
+  return PyUnicode_FromStringAndSize(self->failed->data(), static_cast<Py_ssize_t>(self->failed->size()));
+}
+
+PyMethodDef ws_methods[] = {
+    {"begin", reinterpret_cast<PyCFunction>(ws_begin), METH_O,
+     "begin(want): a response body starts (-2 chunked, -3 until EOF, else its Content-Length)."},
+    {"feed", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(ws_feed)), METH_VARARGS | METH_KEYWORDS,
+     "feed(data, apply=True) -> [(type, new, old)]: the events these body bytes complete."},
+    {nullptr, nullptr, 0, nullptr}};
+
+PyGetSetDef ws_getset[] = {
+    {"items", reinterpret_cast<getter>(ws_get_items), nullptr, "(namespace, name) -> object", nullptr},
+    {"done", reinterpret_cast<getter>(ws_get_done), nullptr, "the body has ended", nullptr},
+    {"failed", reinterpret_cast<getter>(ws_get_failed), nullptr, "why the body cannot be read further, or None",
+     nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr}};
+
+PyType_Slot ws_slots[] = {
+    {Py_tp_doc, const_cast<char*>("An informer's objects, fed with the bytes of its watch response.")},
+    {Py_tp_new, reinterpret_cast<void*>(ws_new)},
+    {Py_tp_dealloc, reinterpret_cast<void*>(ws_dealloc)},
+    {Py_tp_methods, ws_methods},
+    {Py_tp_getset, ws_getset},
+    {0, nullptr}};
+
+PyType_Spec ws_spec = {"_objcore.WatchStore", sizeof(WatchStore), 0, Py_TPFLAGS_DEFAULT, ws_slots};
+
+bool init_watch_store(PyObject* m) {
+  g_str_metadata = PyUnicode_InternFromString("metadata");
+  g_str_namespace = PyUnicode_InternFromString("namespace");
+  g_str_name = PyUnicode_InternFromString("name");
+  g_str_api_version = PyUnicode_InternFromString("apiVersion");
+  g_str_kind = PyUnicode_InternFromString("kind");
+  g_str_empty = PyUnicode_InternFromString("");
+  if (!g_str_metadata || !g_str_namespace || !g_str_name || !g_str_api_version || !g_str_kind || !g_str_empty)
+    return false;
+  PyObject* type = PyType_FromSpec(&ws_spec);
+  if (!type) return false;
+  if (PyModule_AddObject(m, "WatchStore", type) < 0) {
+    Py_DECREF(type);
+    return false;
+  }
+  return true;
+}
+
 PyMethodDef methods[] = {
+    {"canonical", py_canonical, METH_O,
+     "canonical(obj) -> bytes: json.dumps(obj, sort_keys=True, separators=(',', ':')) of a plain JSON tree."},
     {"dumps", py_dumps, METH_O,
      "dumps(obj) -> bytes: compact JSON (json.dumps with separators=(',', ':'), UTF-8) of a JSON tree."},
     {"deepcopy", py_deepcopy, METH_O, "Deep copy of a JSON tree (dict/list; tuples become lists)."},
@@ -1081,5 +1539,10 @@ PyModuleDef module = {PyModuleDef_HEAD_INIT, "_objcore", "Native JSON-tree core"
 
 PyMODINIT_FUNC PyInit__objcore(void) {
   if (!g_keys) g_keys = new std::unordered_map<std::string_view, PyObject*>();
-  return PyModule_Create(&module);
+  PyObject* m = PyModule_Create(&module);
+  if (m && !init_watch_store(m)) {
+    Py_DECREF(m);
+    return nullptr;
+  }
+  return m;
 }

@@ -58,6 +58,7 @@ def targets() -> Dict[str, dict]:
         },
         OBJCORE: {
             "src": [os.path.join(NATIVE, "objcore.cpp")],
+            "deps": [os.path.join(NATIVE, "watch_feed.hpp")],
             "out": os.path.join(NATIVE, OBJCORE),
             "cmd": lambda src, out: [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall",
                                      "-fno-strict-aliasing", f"-I{sysconfig.get_paths()['include']}", *src,

@@ -6,7 +6,8 @@ client (aiohttp) costs ~4× the raw socket round trip per request on this path (
 REST API needs: persistent connections, ``Content-Length`` or ``chunked`` bodies,
 optional TLS, and a streaming mode for watches.  Responses are parsed in the protocol's
 ``data_received`` (one future per response; a watch wakes its consumer once per arrival with
-all the events it holds), not through StreamReader waits.  A pooled connection the server
+all the events it holds — or, given a ``sink``, hands it the body bytes right there, with no
+wake-up at all), not through StreamReader waits.  A pooled connection the server
 closed while idle is skipped; a request that met such a close is retried once unless it is
 a POST.
 """
@@ -117,6 +118,11 @@ class _Conn(asyncio.Protocol):
         self._got = 0
         self._eof = False
         self._no_body = False  # the request in flight is a HEAD
+        # a streaming response with a sink: once a 200 head is in, body bytes go straight to
+        # sink.data() from data_received, and _end resolves when the body or the connection ends
+        self._sink = None
+        self._sink_on = False
+        self._end: Optional[asyncio.Future] = None
 
     # ---------------------------------------------------------------- asyncio.Protocol
 
@@ -124,6 +130,9 @@ class _Conn(asyncio.Protocol):
         self.transport = transport
 
     def data_received(self, data: bytes) -> None:
+        if self._sink_on:
+            self._sink_data(data)
+            return
         self.buf += data
         if self._waiter is not None or self._streaming:
             self._advance()
@@ -134,6 +143,8 @@ class _Conn(asyncio.Protocol):
     def connection_lost(self, exc) -> None:
         self.closed = True
         self._eof = True
+        if self._end is not None and not self._end.done():
+            self._end.set_result(None)
         w, self._waiter = self._waiter, None
         if w is None or w.done():
             return
@@ -172,6 +183,12 @@ class _Conn(asyncio.Protocol):
                     self._waiter = None
                     if w is not None and not w.done():
                         w.set_result(self._head)
+                    if self._sink is not None and status == 200:
+                        self._sink_on = True
+                        data = bytes(self.buf)
+                        self.buf.clear()
+                        self._sink_start(data)
+                        return
             if self._streaming:
                 self._stream_advance()
                 return
@@ -224,6 +241,38 @@ class _Conn(asyncio.Protocol):
             self._waiter = None
             w.set_result(None)
 
+    def _sink_start(self, data: bytes) -> None:
+        try:
+            done = self._sink.begin(self._want)
+        except Exception as e:  # noqa: BLE001 — fails the stream, as in _sink_data
+            self._sink_end(e)
+            return
+        if done:
+            self._sink_end(None)
+        elif data:
+            self._sink_data(data)
+
+    def _sink_data(self, data: bytes) -> None:
+        if self._end.done():
+            return  # bytes after the end of the body, or after the sink failed
+        try:
+            done = self._sink.data(data)
+        except Exception as e:  # noqa: BLE001 — a sink's exception fails its stream, not the loop
+            self._sink_end(e)
+            return
+        if done:
+            self._sink_end(None)
+
+    def _sink_end(self, exc: Optional[BaseException]) -> None:
+        self._eof = True
+        end = self._end
+        if not end.done():
+            if exc is None:
+                end.set_result(None)
+            else:
+                end.set_exception(exc)
+        self.close()
+
     # ---------------------------------------------------------------- client side
 
     async def roundtrip(self, payload: bytes) -> Tuple[int, bytes, bool]:
@@ -236,11 +285,18 @@ class _Conn(asyncio.Protocol):
             self._advance()
         return await w
 
-    async def open_stream(self, payload: bytes) -> Tuple[int, Dict[str, str]]:
+    async def open_stream(self, payload: bytes, sink=None) -> Tuple[int, Dict[str, str]]:
+        """Send a streaming request and wait for the response head.  ``sink``: an object with
+        ``begin(want) -> bool`` (the body starts: -2 chunked, -3 until EOF, else its length) and
+        ``data(bytes) -> bool`` (True: the body has ended); it gets the body of a 200 response
+        as the bytes arrive, in ``data_received`` itself.  Any other status is read as usual."""
         if self.closed:
             raise ConnectionResetError("connection closed")
         self._streaming = True
         self._waiter = w = asyncio.get_running_loop().create_future()
+        if sink is not None:
+            self._sink = sink
+            self._end = asyncio.get_running_loop().create_future()
         self.transport.write(payload)
         got = await w
         if got is None:
@@ -374,10 +430,10 @@ class Http1Pool:
             return status, data
         raise HttpError("unreachable")
 
-    async def stream(self, method: str, target: str) -> Tuple[int, Dict[str, str], "_Stream"]:
+    async def stream(self, method: str, target: str, sink=None) -> Tuple[int, Dict[str, str], "_Stream"]:
         conn = await self._connect()
         try:
-            status, headers = await conn.open_stream(self._head(method, target, None, None))
+            status, headers = await conn.open_stream(self._head(method, target, None, None), sink)
         except BaseException:
             conn.close()
             raise
@@ -425,8 +481,26 @@ class _Stream:
             for line in batch:
                 yield line
 
+    @property
+    def sunk(self) -> bool:
+        """The body goes to the sink the stream was opened with (a 200 response)."""
+        return self.conn._sink_on
+
+    async def wait_end(self) -> None:
+        """Until a sunk body or its connection ends; raises what the sink raised."""
+        try:
+            await self.conn._end
+        finally:
+            self.close()
+
     def close(self) -> None:
         self.conn.close()
+        end = self.conn._end
+        if end is not None:
+            if not end.done():
+                end.set_result(None)
+            elif not end.cancelled():
+                end.exception()  # seen: a failure nobody waited for is not reported at collection
 
 
 # --------------------------------------------------------------------------- server

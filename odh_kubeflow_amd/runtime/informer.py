@@ -14,6 +14,7 @@ objects) and :class:`~odh_kubeflow_amd.runtime.client.EventSource`.
 from __future__ import annotations
 
 import asyncio
+import json
 import logging
 import random
 import time
@@ -24,6 +25,11 @@ from ..models.errors import ApiError, Gone, is_no_match
 from ..models.scheme import SCHEME, ResourceInfo
 from ..utils.selectors import field_matcher, match_labels, parse_field_selector, parse_label_selector, selector_from_dict
 from .client import EventSource, Reader, WatchCallback
+
+try:  # the native watch store (native/objcore.cpp): socket bytes -> cache deltas in one call
+    from ..native._objcore import WatchStore as _WatchStore
+except ImportError:  # pragma: no cover - the extension is not built: the Python path below
+    _WatchStore = None
 
 log = logging.getLogger("runtime.informer")
 
@@ -56,11 +62,67 @@ def strip_data(obj: dict) -> dict:
     return strip_managed_fields(obj)
 
 
+def _takes_store(batches) -> bool:
+    """Whether a client's ``watch_batches`` has the ``store`` parameter (a wrapper or a test
+    double written before it has not)."""
+    import inspect
+
+    try:
+        return "store" in inspect.signature(batches).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 def _one_event_batches(watch):
     async def batches(*args, **kw):
         async for ev in watch(*args, **kw):
             yield [ev]
     return batches
+
+
+class _StoreSink:
+    """The body of an informer's watch response, taken where it arrives: the connection's
+    ``data_received`` calls :meth:`data` with the bytes, the native store turns them into
+    events (framing, decoding against the stored objects, the default transform) and the
+    informer applies them — policy, store, indexes, subscribers — in the loop iteration of the
+    arrival.
+
+    The store decodes only (``feed(apply=False)``): each event goes into ``items`` when its turn
+    comes in :meth:`_Informer._apply`, after the policy that may reject it (another shard's
+    namespace, a label selector the object left), so a subscriber reading the cache from its
+    callback sees the events up to its own and no later one, exactly as on the Python path."""
+
+    def __init__(self, inf: "_Informer", store):
+        self.inf = inf
+        self.store = store
+
+    def begin(self, want: int) -> bool:
+        self.store.begin(want)
+        return self.store.done
+
+    def data(self, data: bytes) -> bool:
+        inf, store = self.inf, self.store
+        inf._backoff = 0.05
+        for et, obj, _ in store.feed(data, False):
+            if et is None:  # a line beyond the native decoder (NaN literals): json's verdict
+                ev = json.loads(obj)
+                et, obj = ev.get("type"), ev.get("object") or {}
+                if et != "ERROR":
+                    inf._apply(et, obj)
+                    continue
+            if et == "ERROR":
+                if inf._rv_waiters:
+                    inf._rv_reached()
+                err = ApiError.from_status(obj)
+                if err.code == 410:
+                    raise Gone(err.message)
+                raise err
+            inf._apply(et, obj, True)
+        if inf._rv_waiters:
+            inf._rv_reached()
+        if store.failed:
+            raise ValueError(store.failed)
+        return store.done
 
 
 class _Informer:
@@ -74,7 +136,16 @@ class _Informer:
         self.label_selector = label_selector
         self.field_selector = field_selector
         self._label_reqs = parse_label_selector(label_selector) if label_selector else None
-        self.items: Dict[Tuple[str, str], dict] = {}
+        # the native store owns the objects (its ``items`` is a plain dict, read and written here
+        # as before) when the kind's transform is the default one, which it applies itself
+        self._sink: Optional[_StoreSink] = None
+        if _WatchStore is not None and cache.transforms.get(info.key, strip_managed_fields) is strip_managed_fields:
+            store = _WatchStore(info.api_version(version), info.kind, bool(info.namespaced))
+            self._sink = _StoreSink(self, store)
+            self.items: Dict[Tuple[str, str], dict] = store.items
+        else:
+            self.items = {}
+        self._backoff = 0.05
         self.by_ns: Dict[str, Set[Tuple[str, str]]] = {}
         self.by_owner: Dict[str, Set[Tuple[str, str]]] = {}
         # (label key, value) -> keys, for the cache's indexed label keys (LABEL_INDEX_KEYS)
@@ -260,14 +331,16 @@ class _Informer:
     def _stored(self, namespace: str, name: str) -> Optional[dict]:
         return self.items.get((namespace if self.info.namespaced else "", name))
 
-    def _apply(self, et: str, obj: dict) -> None:
-        """One watch event into the store, then to the subscribers."""
+    def _apply(self, et: str, obj: dict, transformed: bool = False) -> None:
+        """One watch event into the store, then to the subscribers.  ``transformed``: the native
+        store decoded it, the kind's transform included."""
         self.rv = m.resource_version(obj) or self.rv
         if et == "BOOKMARK":
             return
         if self.ns_filter is not None and not self.ns_filter(m.namespace(obj)):
             return  # a cluster-wide watch: another shard's (or worker's) namespace
-        obj = self._transform(obj)
+        if not transformed:
+            obj = self._transform(obj)
         if et != "DELETED" and self._label_reqs is not None and not match_labels(
                 self._label_reqs, (obj.get("metadata") or {}).get("labels")):
             # the object left the selector: to this cache it is gone
@@ -285,7 +358,7 @@ class _Informer:
 
     async def run(self) -> None:
         ref = f"{self.info.api_version(self.version)}/{self.info.kind}"
-        backoff = 0.05
+        self._backoff = 0.05
         need_list = True
         started: Optional[float] = None
         while True:
@@ -299,12 +372,16 @@ class _Informer:
                 kw = {}
                 if batches is None:  # a client without batched watches (test doubles)
                     batches = _one_event_batches(rest.watch)
+                elif self._sink is not None and _takes_store(batches):
+                    # the native store takes the bytes where they arrive and the events are
+                    # applied there (_StoreSink): nothing comes back here but the stream's end
+                    kw["store"] = self._sink
                 else:  # decoded against the stored object: unchanged subtrees are shared
                     kw["lookup"] = self._stored
                 async for batch in batches(ref, self.namespace, self.rv, labels=self.label_selector,
                                            fields=self.field_selector, timeout_s=self.cache.watch_timeout_s,
                                            **kw):
-                    backoff = 0.05
+                    self._backoff = 0.05
                     for et, obj in batch:
                         self._apply(et, obj)
                     if self._rv_waiters:
@@ -321,14 +398,14 @@ class _Informer:
                     need_list = True
                     continue
                 log.warning("%s watch error: %r", self.info.kind, e)
-                await asyncio.sleep(backoff)
-                backoff = min(backoff * 2, 5.0)
+                await asyncio.sleep(self._backoff)
+                self._backoff = min(self._backoff * 2, 5.0)
             except Exception as e:  # connection reset, server restart
                 log.debug("%s watch dropped: %r", self.info.kind, e)
                 if started is not None and time.monotonic() - started > 1.0:
-                    backoff = 0.05  # the stream was healthy for a while: a fresh drop, not a flapping server
-                await asyncio.sleep(backoff * (1 + random.random()))
-                backoff = min(backoff * 2, 5.0)
+                    self._backoff = 0.05  # the stream was healthy for a while: a fresh drop, not a flapping server
+                await asyncio.sleep(self._backoff * (1 + random.random()))
+                self._backoff = min(self._backoff * 2, 5.0)
 
 
 class _Group:

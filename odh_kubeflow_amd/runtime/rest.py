@@ -31,9 +31,10 @@ try:  # native JSON (native/objcore.cpp): decoding with shared subtrees for watc
     from ..native._objcore import loads_event as _loads_event
     from ..native._objcore import loads_shared as _loads_shared
 
-    def loads_json(raw):
+    def loads_json(raw, old=None):
+        """``json.loads``; the subtrees ``old`` already holds unchanged are ``old``'s, not copies."""
         try:
-            return _loads_shared(raw)
+            return _loads_shared(raw, old)
         except ValueError:
             return json.loads(raw)  # json's own verdict (and its NaN / Infinity literals)
 
@@ -46,7 +47,9 @@ try:  # native JSON (native/objcore.cpp): decoding with shared subtrees for watc
             return json.dumps(obj, separators=(",", ":")).encode()
 except ImportError:  # pragma: no cover - the extension is not built
     _loads_event = None
-    loads_json = json.loads
+
+    def loads_json(raw, old=None):
+        return json.loads(raw)
 
     def dumps_json(obj) -> bytes:
         return json.dumps(obj, separators=(",", ":")).encode()
@@ -297,7 +300,11 @@ class RestClient(Client):
         return self.base + info.path(version, namespace if info.namespaced else None, name, sub)
 
     async def request(self, method: str, url: str, body: Any = None, params: Optional[dict] = None,
-                      content_type: str = "application/json", count_as: str = "other") -> dict:
+                      content_type: str = "application/json", count_as: str = "other",
+                      share: Optional[dict] = None) -> dict:
+        """``share``: an object the response is nearly a copy of (the one a create or update
+        sends, which the response then replaces): decoded against it, what the server left
+        alone is that object's own subtrees, not new ones."""
         from urllib.parse import urlencode
 
         await self._bucket.take()
@@ -316,7 +323,7 @@ class RestClient(Client):
         if raw:
             self.bytes_in[count_as] = self.bytes_in.get(count_as, 0) + len(raw)
         try:
-            out = loads_json(raw) if raw else {}
+            out = loads_json(raw, share) if raw else {}
         except ValueError:
             out = {"message": raw[:200].decode(errors="replace")}
         if status >= 400:
@@ -420,18 +427,18 @@ class RestClient(Client):
     async def create(self, obj):
         info, v = _info_and_version(obj)
         ns = (obj.get("metadata") or {}).get("namespace")
-        return _refresh(obj, await self.request("POST", self.path(info, v, ns), obj))
+        return _refresh(obj, await self.request("POST", self.path(info, v, ns), obj, share=obj))
 
     async def update(self, obj):
         info, v = _info_and_version(obj)
         md = obj.get("metadata") or {}
-        return _refresh(obj, await self.request("PUT", self.path(info, v, md.get("namespace"), md.get("name")), obj))
+        return _refresh(obj, await self.request("PUT", self.path(info, v, md.get("namespace"), md.get("name")), obj, share=obj))
 
     async def update_status(self, obj):
         info, v = _info_and_version(obj)
         md = obj.get("metadata") or {}
         return _refresh(obj, await self.request("PUT", self.path(info, v, md.get("namespace"), md.get("name"),
-                                                                 "status"), obj))
+                                                                 "status"), obj, share=obj))
 
     async def patch(self, obj_or_kind, patch, patch_type="merge", name=None, namespace=None, subresource=None):
         if isinstance(obj_or_kind, dict):
@@ -467,14 +474,19 @@ class RestClient(Client):
 
     async def watch_batches(self, kind, namespace=None, resource_version: Optional[str] = None, labels=None,
                             fields=None, timeout_s: int = 300, bookmarks: bool = True,
-                            lookup=None) -> AsyncIterator[List[Tuple[str, dict]]]:
+                            lookup=None, store=None) -> AsyncIterator[List[Tuple[str, dict]]]:
         """Yield the ``(type, object)`` events of each arrival as one list (an informer applies
         them in one go); raises :class:`Gone` when the RV is too old — after yielding the
         events that preceded the ERROR in its batch.
 
         ``lookup(namespace, name)``: the caller's current copy of an object (an informer's
         store).  Events are decoded natively (``native/objcore.cpp`` ``loads_event``) against
-        it: the subtrees a change leaves alone are the stored ones, not new copies."""
+        it: the subtrees a change leaves alone are the stored ones, not new copies.
+
+        ``store``: a sink (``begin(want)`` / ``data(bytes)``, see ``http1._Conn.open_stream``)
+        that takes the body bytes of the watch as they arrive, in the connection's own
+        ``data_received`` — an informer's native store.  Nothing is yielded then: the iteration
+        ends when the stream does, and raises what the sink raised (``Gone`` for a 410 event)."""
         from urllib.parse import urlencode
 
         info, v = _info_and_version(kind)
@@ -493,12 +505,12 @@ class RestClient(Client):
         target = self.path(info, v, namespace)[len(self.base):] + "?" + urlencode(params)
         pool = self._http()
         sent = self._sent_token
-        status, _headers, stream = await pool.stream("GET", target)
+        status, _headers, stream = await pool.stream("GET", target, sink=store)
         if status == 401 and self.tokens is not None:
             await stream.read_all()
             stream.close()
             if self._unauthorized_retry(status, sent):  # rotated token: reopen once with the new one
-                status, _headers, stream = await self._http().stream("GET", target)
+                status, _headers, stream = await self._http().stream("GET", target, sink=store)
             else:
                 status, _headers, stream = 401, _headers, None
         if stream is None:
@@ -509,6 +521,9 @@ class RestClient(Client):
                 raise ApiError.from_status(json.loads(raw), status)
             except ValueError:
                 raise InternalError(raw[:200].decode(errors="replace"))
+        if stream.sunk:
+            await stream.wait_end()
+            return
         loads = json.loads
         native = _loads_event
         try:

@@ -11,7 +11,6 @@ template changed, scales down to ``replicas``, and maintains ``status``
 from __future__ import annotations
 
 import hashlib
-import json
 import logging
 from typing import Optional
 
@@ -19,7 +18,7 @@ from ...models import kinds
 from ...models import meta as m
 from ...models.errors import ApiError, is_already_exists, is_conflict, is_not_found
 from ...runtime.controller import Request, Result, enqueue_for_owner
-from ...utils.objutil import deepcopy_json
+from ...utils.objutil import canonical_json, deepcopy_json
 
 log = logging.getLogger(__name__)
 
@@ -47,8 +46,7 @@ def worker_owns(ns: dict, index: int) -> bool:
 
 def template_hash(sts: dict) -> str:
     tmpl = (sts.get("spec") or {}).get("template") or {}
-    h = hashlib.sha1(json.dumps(tmpl, sort_keys=True, separators=(",", ":")).encode(),
-                    usedforsecurity=False).hexdigest()[:10]
+    h = hashlib.sha1(canonical_json(tmpl), usedforsecurity=False).hexdigest()[:10]
     return f"{m.name(sts)}-{h}"
 
 

@@ -10,6 +10,7 @@ recursion otherwise.
 
 from __future__ import annotations
 
+import json
 from typing import Any, Iterable, Optional
 
 
@@ -106,12 +107,25 @@ def _py_equal_except(a: dict, b: dict, keys) -> bool:
     return ({**a, "metadata": ma} if "metadata" in a else a) == ({**b, "metadata": mb} if "metadata" in b else b)
 
 
+def _py_canonical_json(o: Any) -> bytes:
+    return json.dumps(o, sort_keys=True, separators=(",", ":")).encode()
+
+
 if NATIVE_OBJCORE:
     semantic_equal = _objcore.semantic_equal
     equal_except = _objcore.equal_except
+
+    def canonical_json(o: Any) -> bytes:
+        """``json.dumps(o, sort_keys=True, separators=(",", ":"))`` as bytes — a content key or
+        hash input; natively for plain JSON trees, through json for anything else."""
+        try:
+            return _objcore.canonical(o)
+        except (TypeError, ValueError):
+            return _py_canonical_json(o)
 else:  # pragma: no cover
     semantic_equal = _py_semantic_equal
     equal_except = _py_equal_except
+    canonical_json = _py_canonical_json
 
 
 def find_by_name(items: Optional[Iterable[dict]], name: str) -> Optional[dict]:

@@ -16,14 +16,13 @@ and issues an Update per reconcile against a real apiserver.
 
 from __future__ import annotations
 
-import json
 from collections import OrderedDict
 from typing import Callable, Optional
 
 from ..models import defaults
 from ..models import meta as m
 from ..models.errors import is_not_found
-from .objutil import deepcopy_json, ensure_dict
+from .objutil import canonical_json, deepcopy_json, ensure_dict
 
 
 def _copy_meta(frm: dict, to: dict) -> bool:
@@ -48,14 +47,14 @@ def _copy_meta(frm: dict, to: dict) -> bool:
     return require
 
 
-_DEFAULTED: "OrderedDict[str, dict]" = OrderedDict()  # canonical JSON of a desired pod spec -> defaulted
+_DEFAULTED: "OrderedDict[bytes, dict]" = OrderedDict()  # canonical JSON of a desired pod spec -> defaulted
 _DEFAULTED_MAX = 1024
 
 
 def _defaulted(spec: dict) -> dict:
     """``defaults.pod_spec`` of a desired spec, remembered by content: a notebook's desired spec
     is regenerated identical on every reconcile of one generation."""
-    key = json.dumps(spec, sort_keys=True, separators=(",", ":"))
+    key = canonical_json(spec)
     hit = _DEFAULTED.get(key)
     if hit is None:
         hit = _DEFAULTED[key] = defaults.pod_spec(deepcopy_json(spec))
