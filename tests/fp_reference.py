@@ -53,6 +53,15 @@ def tiles(fmt, m, n):
     return (m // 256) * (n // TILE_N[fmt])
 
 
+def sweep_values(fmt, v, side):
+    """The integers of A (``side`` 0) or Bt (1) with element ``x mod K`` of every row x one step of the
+    family, ``MUL_A`` resp. ``MUL_B``, higher: at most ``3 MUL_A`` resp. ``4 MUL_B`` in magnitude."""
+    out = np.array(v, dtype=np.int64)
+    idx = np.arange(out.shape[0])
+    out[idx, idx % out.shape[1]] += MUL[fmt][side]
+    return out
+
+
 # ------------------------------------------------------------------ value against value
 
 

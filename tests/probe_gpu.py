@@ -1,6 +1,6 @@
-"""What the GPU test files of the probe's low-precision kernels share (``test_gpu_mx_exact.py``,
-``test_gpu_mx_formats_exact.py``, ``test_gpu_dense_exact.py``, ``test_gpu_lowprec_sweeps.py``): the
-device fixture and the per-test timeout, which they import by name, the probe operands of a
+"""What the GPU test files of the probe's matrix-core kernels share (``test_gpu_mx_exact.py``,
+``test_gpu_mx_formats_exact.py``, ``test_gpu_dense_exact.py``, ``test_gpu_lowprec_sweeps.py``,
+``test_gpu_sparse_fp_sweeps.py``): the device fixture and the per-test timeout, which they import by name, the probe operands of a
 format next to their host model, the sweeps that change one element per launch, the store
 checks, and the run of ``odh-gpu-probe``.
 
@@ -18,8 +18,10 @@ import types
 import numpy as np
 import pytest
 
+import fp_reference as fp
 import mx_reference as mx
 import probe_reference as ref
+import sparse_reference as sp
 
 torch = pytest.importorskip("torch")
 
@@ -72,13 +74,54 @@ def _probe(fmt, m, n, k):
     """The probe operands of ``fmt`` on the GPU (written by the library's fill and compared with
     the model once), the model's copies on the host, the expected C, a ``product(host)`` that
     multiplies host operands in float64 / int64, and a ``launch(tile_xcd_ptr, counters_ptr)`` of
-    the fused check.  Shared between tests: every test leaves the operands as it found them."""
+    the fused check.  Shared between tests: every test leaves the operands as it found them.
+
+    ``fmt`` names an MX format, ``f16`` / ``i8`` (dense), ``f32`` / ``f64``, or a 2:4 sparse format as
+    ``sp:bf16``, ``sp:f16``, ``sp:i8``, ``sp:fp8``, ``sp:bf8``.  The sparse tensors ``ac``, ``meta``, ``bt`` and their
+    host copies are the elements as stored (``sparse_reference.NP_STORED``: bf16 as the int16 of its bits,
+    fp8 and bf8 as codes), so that numpy holds them.  ``tile_n`` is the width of a workgroup's tile."""
     gpu = _gpu()
     lib = gpu.load_library()
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    p = types.SimpleNamespace(fmt=fmt, m=m, n=n, k=k, device=dev)
-    if fmt in mx.NAMES:
+    p = types.SimpleNamespace(fmt=fmt, m=m, n=n, k=k, device=dev, tile_n=256)
+    if fmt.startswith("sp:"):
+        sfmt = fmt[3:]
+        code = gpu.SPARSE_FORMATS[sfmt]
+        dtype = gpu._sparse_dtype(code)
+        ac = torch.zeros((m, k // 2), dtype=dtype, device=dev)
+        meta = torch.full((m, k // 8), 0x77, dtype=torch.uint8, device=dev)
+        bt = torch.zeros((n, k), dtype=dtype, device=dev)
+        table = torch.full(gpu.SPARSE_TABLE, -1, dtype=torch.int32, device=dev)
+        gpu.sparse_fill(sfmt, ac, meta, bt, table)
+        stored = torch.from_numpy(np.zeros(1, dtype=sp.NP_STORED[sfmt])).dtype
+        t = {"ac": ac.view(stored), "meta": meta, "bt": bt.view(stored)}
+        hac, hmeta, hbt = sp.fill(sfmt, m, n, k)
+        p.values = (hac, hbt)
+        p.host = {"ac": sp.encode(sfmt, hac), "meta": hmeta, "bt": sp.encode(sfmt, hbt)}
+        p.expect = sp.expected(sfmt, m, n, k)
+        assert np.array_equal(table.cpu().numpy().astype(np.int64), sp.table(k))
+        # times nothing: the fill has applied the i8 multipliers
+        p.product = lambda h: sp.product(sp.decode(sfmt, h["ac"]), h["meta"], sp.decode(sfmt, h["bt"]))
+
+        def launch(tile_xcd, counters):
+            gpu._check(lib.odh_sparse_probe_gemm_verify(code, ac.data_ptr(), meta.data_ptr(), bt.data_ptr(),
+                                                        table.data_ptr(), m, n, k, tile_xcd, counters, stream))
+    elif fmt in fp.FORMATS:
+        code = gpu.FP_FORMATS[fmt]
+        p.tile_n = fp.TILE_N[fmt]
+        dtype = torch.float64 if fmt == "f64" else torch.float32
+        t = {"a": torch.full((m, k), 77, dtype=dtype, device=dev), "bt": torch.full((n, k), 77, dtype=dtype, device=dev)}
+        gpu.fp_fill(fmt, t["a"], t["bt"])
+        p.values = fp.operand_values(fmt, m, n, k)
+        p.host = dict(zip(("a", "bt"), fp.operands(fmt, m, n, k)))
+        p.expect = fp.expected(fmt, m, n, k)
+        p.product = lambda h: h["a"].astype(np.int64) @ h["bt"].astype(np.int64).T
+
+        def launch(tile_xcd, counters):
+            gpu._check(lib.odh_fp_probe_gemm_verify(code, t["a"].data_ptr(), t["bt"].data_ptr(), m, n, k,
+                                                    tile_xcd, counters, stream))
+    elif fmt in mx.NAMES:
         code = p.code = mx.NAMES[fmt]
         a, bt, sa, sbt, table = _mx_filled(dev, fmt, m, n, k)
         t = {"a": a, "bt": bt, "sa": sa, "sbt": sbt}
@@ -126,23 +169,34 @@ def _assert_operands_are_the_models(p):
         assert np.array_equal(_bits(p.t[name].cpu().numpy()), _bits(host)), f"{p.fmt} {name} differs from the model"
 
 
+ROW_OPERANDS = {"a", "sa", "ac", "meta"}  # a changed element of row i changes row i of the product
+COLUMN_OPERANDS = {"bt", "sbt"}
+
+
 def _sweep(p, name, wrong_host, rows):
-    """``wrong_host`` is the model's ``name`` (``a``, ``bt``, ``sa`` or ``sbt``) with one element of
-    every row changed: one array element, or one or two adjacent bytes of a packed 6-bit row.
+    """``wrong_host`` is the model's ``name`` (``a``, ``bt``, ``sa``, ``sbt``, or the sparse ``ac`` or ``meta``) with
+    one element of every row changed: one array element, one or two adjacent bytes of a packed
+    6-bit row, or the metadata byte that holds a changed nibble.
     Launch x runs with only row x's element changed, into counter row x and tile map x, and
     restores it; everything is read back once at the end.
 
     A changed element of row i of A (or of its scales) changes only row i of the product, so row
     i of the product of ``wrong_host`` with the other, clean operands is launch i's row i, and
-    every other row of that launch is clean.  For Bt and its scales the same holds of columns."""
+    every other row of that launch is clean.  For Bt and its scales the same holds of columns.
+
+    A workgroup's tile is 256 rows by ``p.tile_n`` columns (128 for f64), so a row's line crosses tiles
+    of ``p.tile_n`` and a column's line tiles of 256; every kernel books tile ``(tm, tn)`` at
+    ``tile_xcd[tm * tiles_n + tn]``."""
     gpu = _gpu()
     m, n = p.m, p.n
-    tiles_m, tiles_n = m // 256, n // 256
+    tile_n = p.tile_n
+    tiles_m, tiles_n = m // 256, n // tile_n
     tiles = tiles_m * tiles_n
     count = m if rows else n
     target, clean_host = p.t[name], p.host[name]
     width = target.shape[1]
-    assert (name in ("a", "sa")) == rows and wrong_host.shape == clean_host.shape == (count, width)
+    assert name in ROW_OPERANDS | COLUMN_OPERANDS and (name in ROW_OPERANDS) == rows
+    assert wrong_host.shape == clean_host.shape == (count, width) and wrong_host.dtype == clean_host.dtype
     diff = wrong_host != clean_host
     first = diff.argmax(axis=1)
     last = width - 1 - diff[:, ::-1].argmax(axis=1)
@@ -170,12 +224,13 @@ def _sweep(p, name, wrong_host, rows):
     lines = mismatch if rows else mismatch.T  # [x][position along launch x's line]
     want_err = lines.sum(axis=1)
     assert (want_err > 0).all(), "a launch that expects no mismatch checks nothing"
-    per_tile = lines.reshape(count, -1, 256).sum(axis=2)  # [x][tile along the line]
+    per_tile = lines.reshape(count, -1, tile_n if rows else 256).sum(axis=2)  # [x][tile along the line]
+    assert per_tile.shape[1] == (tiles_n if rows else tiles_m)
     assert ((tx >= 0) & (tx < gpu.N_XCD)).all(), tx[((tx < 0) | (tx >= gpu.N_XCD)).any(axis=1)][:4]
     want_xcd = np.zeros((count, gpu.N_XCD), dtype=np.int64)
     for x in range(count):
         for t in range(per_tile.shape[1]):
-            tm, tn = (x // 256, t) if rows else (t, x // 256)
+            tm, tn = (x // 256, t) if rows else (t, x // tile_n)
             want_xcd[x, tx[x, tm * tiles_n + tn]] += per_tile[x, t]
     what = f"{p.fmt} {name} " + ("row" if rows else "column")
     got_err = h[:, gpu.ODH_SLOT_GEMM_ERR].astype(np.int64) & 0xFFFFFFFF

@@ -138,7 +138,7 @@ def bf8_code(v):
 
 
 def fp8_value(code):
-    """The value of an e4m3fn code (no NaN codes expected)."""
+    """The value of an e4m3fn code (no NaN codes expected: ``code_values`` has them)."""
     c = np.asarray(code, dtype=np.int64)
     e, mant = (c >> 3) & 15, c & 7
     mag = np.where(e == 0, mant / 8.0 * 2.0 ** -6, (1 + mant / 8.0) * 2.0 ** (e - 7))
@@ -146,11 +146,56 @@ def fp8_value(code):
 
 
 def bf8_value(code):
-    """The value of an e5m2 code (no inf / NaN codes expected)."""
+    """The value of an e5m2 code (no inf / NaN codes expected: ``code_values`` has them)."""
     c = np.asarray(code, dtype=np.int64)
     e, mant = (c >> 2) & 31, c & 3
     mag = np.where(e == 0, mant / 4.0 * 2.0 ** -14, (1 + mant / 4.0) * 2.0 ** (e - 15))
     return np.where(c & 0x80, -mag, mag)
+
+
+def code_values(fmt):
+    """All 256 codes of ``fp8`` (OCP e4m3fn: S.1111.111 is NaN, no infinity, largest ±448) or ``bf8`` (OCP
+    e5m2: exponent 31 is ±inf with mantissa 0 and NaN otherwise, largest ±57344) as float64."""
+    c = np.arange(256, dtype=np.int64)
+    if fmt == "fp8":
+        v = fp8_value(c)
+        v[(c & 0x7F) == 0x7F] = np.nan
+        return v
+    assert fmt == "bf8"
+    v = bf8_value(c)
+    top = (c >> 2) & 31 == 31
+    v[top & (c & 3 != 0)] = np.nan
+    v[top & (c & 3 == 0)] = np.where(c[top & (c & 3 == 0)] & 0x80, -np.inf, np.inf)
+    return v
+
+
+# the elements as they are stored: bf16 as the int16 of its bits (numpy has no bfloat16), fp8 / bf8 as codes
+NP_STORED = {"bf16": np.int16, "f16": np.float16, "i8": np.int8, "fp8": np.uint8, "bf8": np.uint8}
+
+
+def encode(fmt, ints):
+    """Small integers (the probe's: ``|v| <= 3``; bf16, f16 and i8: any the format holds) as stored elements."""
+    v = np.asarray(ints, dtype=np.int64)
+    if fmt == "bf16":
+        bits = v.astype(np.float32).view(np.uint32)
+        assert not (bits & 0xFFFF).any()  # 8 significant bits
+        return (bits >> 16).astype(np.uint16).view(np.int16)
+    if fmt in ("fp8", "bf8"):
+        return (fp8_code if fmt == "fp8" else bf8_code)(v)
+    out = v.astype(NP_STORED[fmt])
+    assert np.array_equal(out.astype(np.int64), v)
+    return out
+
+
+def decode(fmt, stored):
+    """Stored elements as float64, every bit pattern: subnormals, infinities and NaN included."""
+    x = np.asarray(stored)
+    assert x.dtype == NP_STORED[fmt], (fmt, x.dtype)
+    if fmt == "bf16":
+        return (x.view(np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    if fmt in ("fp8", "bf8"):
+        return code_values(fmt)[x]
+    return x.astype(np.float64)
 
 
 # ------------------------------------------------------------------ the product and its mismatches
@@ -170,6 +215,19 @@ def product_per_slot(ac, nib, bt):
     sel = np.stack((nib & 3, nib >> 2), axis=-1).reshape(m, 2 * g)
     kd = 4 * (np.arange(2 * g) // 2)[None, :] + sel
     return np.stack([(ac * bt[j][kd]).sum(axis=1) for j in range(bt.shape[0])], axis=1)
+
+
+def product_per_slot_f64(ac, nib, bt):
+    """``product_per_slot`` in float64, for operands with an infinity or a NaN.  Only the kept slots
+    multiply: a row meets ``Bt[j][k]`` only if it keeps dense position k, and then also with a kept
+    zero, and ``0 · inf`` and ``0 · NaN`` are NaN.  (``decompress(...) @ bt.T`` would multiply the pruned
+    positions too and turn every row of the column into NaN.)"""
+    ac, bt, nib = np.asarray(ac, dtype=np.float64), np.asarray(bt, dtype=np.float64), np.asarray(nib, dtype=np.int64)
+    m, g = nib.shape
+    sel = np.stack((nib & 3, nib >> 2), axis=-1).reshape(m, 2 * g)
+    kd = 4 * (np.arange(2 * g) // 2)[None, :] + sel
+    with np.errstate(invalid="ignore"):
+        return np.stack([(ac * bt[j][kd]).sum(axis=1) for j in range(bt.shape[0])], axis=1)
 
 
 def mismatches(fmt, ac, meta, bt, k):
@@ -266,3 +324,140 @@ def lanemap_case(fmt):
     assert all(len(set(row.tolist())) == stage for row in values[:3])
     want = values[:, kd].T.copy()  # C[i][j] = Bt[j][kd_i]
     return ac, pack_meta(nib), bt, want
+
+
+# ------------------------------------------------------------------ sweeps of the fused check
+
+
+def other_value(v, mul=1):
+    """Another small value of both families than ``v`` (multiples of ``mul``): 1, or 2 where it is 1."""
+    v = np.asarray(v, dtype=np.int64)
+    return np.where(v != mul, mul, 2 * mul)
+
+
+def sweep_values(fmt, v, side):
+    """The integers of the compressed A (``side`` 0) or of Bt (1) with element ``x mod width`` of every row x
+    replaced by another value of the family, times the format's multiplier."""
+    out = np.array(v, dtype=np.int64)
+    idx = np.arange(out.shape[0])
+    hot = idx % out.shape[1]
+    out[idx, hot] = other_value(out[idx, hot], MUL[fmt][side])
+    return out
+
+
+def kept_slot_coordinates(fmt, slot):
+    """Where kept slot ``slot`` of a compressed row lives in the kernel: ``(stage, instruction of the
+    stage, lane half, group of the lane's eight or sixteen bytes, slot of the group)``.  A stage is 64
+    bytes of a compressed row, an instruction 32 of them, a lane half 16."""
+    byte = np.asarray(slot, dtype=np.int64) * ESIZE[fmt]
+    per_half = 16 // ESIZE[fmt]  # kept elements of a lane
+    return byte // 64, byte % 64 // 32, byte % 32 // 16, np.asarray(slot) % per_half // 2, np.asarray(slot) % 2
+
+
+def nibble_sweep_plan(m, n, k):
+    """One metadata nibble per row for a sweep of the fused check: ``(group [m], replacement [m], moved)``.
+
+    The candidates of row i are the pairs (group, replacement) in cyclic order, six valid nibbles per
+    group, from group ``i mod (K/4)`` and replacement number ``(i + i // (K/4) + 2) mod 6`` on (an offset at
+    which few rows start on the nibble they already have); the plan takes
+    the first under which row i of the product leaves the table in at least one column.  (The
+    nibble the row has there changes nothing, and neither does moving the selector of a kept zero
+    or between two positions at which ``Bt`` agrees in every column.)  ``moved`` counts the rows that did
+    not take their first candidate.  The multipliers of i8 are not zero and change no mismatch, so
+    the plan serves every format."""
+    a, bt = ref.probe_operands(m, n, k)
+    nib = nibbles(m, k)
+    ac = compress_with(a, nib)
+    groups = k // 4
+    group, new, moved = np.empty(m, dtype=np.int64), np.empty(m, dtype=np.int64), 0
+    for i in range(m):
+        first = (i % groups) * 6 + (i + i // groups + 2) % 6
+        for t in range(6 * groups):
+            q = (first + t) % (6 * groups)
+            g, cand = q // 6, VALID_NIBBLES[q % 6]
+            old = int(nib[i, g])
+            delta = np.zeros(n, dtype=np.int64)
+            for s, (was, now) in enumerate(((old & 3, cand & 3), (old >> 2, cand >> 2))):
+                delta += ac[i, 2 * g + s] * (bt[:, 4 * g + now] - bt[:, 4 * g + was])
+            if delta.any():
+                break
+        else:
+            raise AssertionError(f"row {i}: no nibble changes the product")
+        group[i], new[i] = g, cand
+        moved += t > 0
+    return group, new, moved
+
+
+def meta_with_nibbles(meta, group, new):
+    """The metadata bytes with nibble ``group[i]`` of row i replaced by ``new[i]``."""
+    nib = unpack_meta(meta)
+    nib[np.arange(nib.shape[0]), group] = new
+    return pack_meta(nib)
+
+
+# ------------------------------------------------------------------ store kernel: value against value
+
+
+def bf16_value_sets():
+    """Two sets of 256 bf16 bit patterns (uint16) whose every product big · small is a normal fp32 or a
+    zero, and exact (8 + 8 significant bits): no set holding both the largest finite value and the
+    smallest normal can do that with itself, so they stand on opposite sides, and the case is
+    run both ways round.
+    ``big``: the integers -8 .. 8, ± the largest finite value, ±0, the all-ones mantissa of every exponent
+    2^0 .. 2^126, and seeded normals of magnitude in [1, 2^128).
+    ``small``: the smallest normal, ±0, the all-ones mantissa of every exponent 2^-126 .. 2^-2, and seeded
+    normals of magnitude in [2^-126, 2^-1)."""
+    rng = np.random.default_rng(161616)
+
+    def normals(count, lo, hi):  # biased exponents lo .. hi
+        e = rng.integers(lo, hi + 1, size=count)
+        return (rng.integers(0, 2, size=count) << 15) | (e << 7) | rng.integers(0, 128, size=count)
+
+    ints = (np.arange(-8, 9).astype(np.float32).view(np.uint32) >> 16).tolist()
+    big = ints + [0x7F7F, 0xFF7F, 0x0000, 0x8000] + [(e << 7) | 0x7F for e in range(127, 254)]
+    big += normals(256 - len(big), 127, 254).tolist()
+    small = [0x0080, 0x0000, 0x8000] + [(e << 7) | 0x7F for e in range(1, 126)]
+    small += normals(256 - len(small), 1, 125).tolist()
+    return np.array(big, dtype=np.uint16), np.array(small, dtype=np.uint16)
+
+
+def store_values(fmt, swap=False):
+    """The 256 stored elements of the rows and of the columns of ``onehot_case``: every code of fp8 and
+    bf8 and every value of i8 on both sides, the halves of ``probe_reference.f16_values`` on both, and
+    for bf16 the two sets of ``bf16_value_sets`` (``swap``: the small one on the rows)."""
+    if fmt in ("fp8", "bf8"):
+        v = np.arange(256, dtype=np.uint8)
+        return v, v
+    if fmt == "i8":
+        v = np.arange(256, dtype=np.uint8).view(np.int8)
+        return v, v
+    if fmt == "f16":
+        v = ref.f16_values().view(np.float16)
+        return v, v
+    big, small = (x.view(np.int16) for x in bf16_value_sets())
+    return (small, big) if swap else (big, small)
+
+
+def onehot_case(fmt, swap=False):
+    """256 × 256 at one stage, every output one product: compressed row i holds row value i in kept slot
+    ``i mod (stage / 2)`` and +0 elsewhere (over the rows: every slot of the stage), the metadata is
+    seeded random valid nibbles, and ``Bt[j]`` is column value j at every k, so whatever the nibbles
+    select the expectation is the same.  Returns ``ac, meta, bt`` as stored and ``want`` in float64,
+    the IEEE product ``row value i · column value j``: NaN for a NaN and for ``inf · 0``, the same-signed
+    infinity for ``inf · x``.  The row's other kept slots are zeros and are multiplied too, so an
+    infinite or NaN column value makes its whole column NaN (``0 · inf``), while a NaN or infinite
+    row value meets only its own slot."""
+    stage = STAGE[fmt]
+    half = stage // 2
+    rows, cols = store_values(fmt, swap)
+    i = np.arange(256)
+    ac = np.zeros((256, half), dtype=NP_STORED[fmt])  # all bits 0 is +0 in every format
+    ac[i, i % half] = rows
+    rng = np.random.default_rng(2400024 + FORMATS.index(fmt))
+    meta = pack_meta(rng.choice(VALID_NIBBLES, size=(256, stage // 4)))
+    bt = np.repeat(cols[:, None], stage, axis=1)
+    va, vb = decode(fmt, rows), decode(fmt, cols)
+    with np.errstate(invalid="ignore"):
+        want = va[:, None] * vb[None, :]
+    want = np.where(np.isfinite(vb)[None, :], want, np.nan)
+    return ac, meta, bt, want

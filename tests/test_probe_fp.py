@@ -296,3 +296,28 @@ def test_onehot_case_is_one_rounded_product_per_output(fmt):
             ulp = Fraction(float(np.spacing(np.abs(want[x, y]))))
             assert abs(got - exact) * 2 <= ulp, (x, y)
     assert np.array_equal(want, va[:, None] * vb[None, :])
+
+
+@pytest.mark.parametrize("fmt", fp.FORMATS)
+def test_swept_operands_stay_exact_and_no_launch_is_vacuous(fmt):
+    """The operands of the GPU sweeps (``test_gpu_sparse_fp_sweeps.py``): 512 × 512 at 7 stages."""
+    m = n = 512
+    k = 7 * fp.STAGE[fmt]
+    assert k == {"f32": 112, "f64": 56}[fmt] and k % 35 != 0 and fp.k_exact(fmt, k) and gpu.fp_k_exact(fmt, k)
+    assert k // fp.STAGE[fmt] > 4  # more stages than ring slots
+    assert fp.tiles(fmt, m, n) == {"f32": 4, "f64": 8}[fmt] and n // fp.TILE_N[fmt] == {"f32": 2, "f64": 4}[fmt]
+    va, vb = fp.operand_values(fmt, m, n, k)
+    expect = fp.expected(fmt, m, n, k)
+    assert np.array_equal(va @ vb.T, expect)
+    for side, clean, other in ((0, va, vb), (1, vb, va)):
+        wrong = fp.sweep_values(fmt, clean, side)
+        x = np.arange(512)
+        assert np.array_equal(np.argwhere(wrong != clean), np.stack([x, x % k], axis=1))
+        assert np.array_equal((wrong - clean)[x, x % k], np.full(512, fp.MUL[fmt][side]))
+        # exact: with every changed element at once the sums of magnitudes stay below the accumulator's
+        # integer range, and the floats are the integers
+        assert (np.abs(wrong) @ np.abs(other).T).max() < fp.EXACT_BELOW[fmt]
+        assert np.array_equal(wrong.astype(fp.NP_DTYPE[fmt]).astype(np.int64), wrong)
+        mismatch = (wrong @ vb.T if side == 0 else va @ wrong.T) != expect
+        counts = (mismatch if side == 0 else mismatch.T).sum(axis=1)
+        assert set(counts.tolist()) == ({438, 439} if side == 0 else {409, 410})

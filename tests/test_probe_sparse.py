@@ -409,3 +409,180 @@ def test_compress_refuses_and_prunes():
         gpu.sparse_decompress(torch.zeros((2, 4)), torch.zeros((2, 2), dtype=torch.uint8))
     with pytest.raises(ValueError):
         gpu.sparse_decompress(torch.zeros((2, 4)), torch.zeros((2, 1), dtype=torch.int8))
+
+
+# ------------------------------------------------------------------ the models of the sweeps and the value cases
+
+
+SWEEP = (512, 512, 640)  # the shape of tests/test_gpu_sparse_fp_sweeps.py
+
+
+@pytest.mark.parametrize("fmt", ["fp8", "bf8"])
+def test_code_values_are_torchs_for_every_code(fmt):
+    codes = np.arange(256, dtype=np.uint8)
+    theirs = torch.from_numpy(codes).view(torch.float8_e4m3fn if fmt == "fp8" else torch.float8_e5m2).double().numpy()
+    ours = sp.code_values(fmt)
+    assert np.array_equal(np.isnan(ours), np.isnan(theirs)) and np.array_equal(ours[~np.isnan(ours)], theirs[~np.isnan(theirs)])
+    assert np.array_equal(np.signbit(ours[~np.isnan(ours)]), np.signbit(theirs[~np.isnan(theirs)]))  # -0 is -0
+    if fmt == "fp8":
+        assert np.flatnonzero(np.isnan(ours)).tolist() == [0x7F, 0xFF] and not np.isinf(ours).any()
+        assert np.nanmax(ours) == 448 and ours[1] == 2.0 ** -9
+    else:
+        assert np.flatnonzero(np.isnan(ours)).tolist() == [0x7D, 0x7E, 0x7F, 0xFD, 0xFE, 0xFF]
+        assert ours[0x7C] == np.inf and ours[0xFC] == -np.inf and ours[0x7B] == 57344 and ours[1] == 2.0 ** -16
+
+
+@pytest.mark.parametrize("fmt", sp.FORMATS)
+def test_stored_elements_round_trip(fmt):
+    m, n, k = 30, 7, 128
+    hac, hmeta, hbt = sp.fill(fmt, m, n, k)
+    for ints in (hac, hbt):
+        stored = sp.encode(fmt, ints)
+        assert stored.dtype == sp.NP_STORED[fmt] and stored.itemsize == sp.ESIZE[fmt]
+        assert np.array_equal(sp.decode(fmt, stored), ints)
+        assert not np.signbit(sp.decode(fmt, stored)[ints == 0]).any()  # the fill writes no -0
+    if fmt == "bf16":
+        t = torch.from_numpy(sp.encode(fmt, hbt)).view(torch.bfloat16)
+        assert np.array_equal(t.double().numpy(), hbt)
+        bits = np.array([0x7FC0, 0x7F80, 0xFF80, 0x0080, 0x7F7F], dtype=np.uint16).view(np.int16)
+        got = sp.decode(fmt, bits)
+        assert np.isnan(got[0]) and got[1:].tolist() == [np.inf, -np.inf, 2.0 ** -126, (2 - 2.0 ** -7) * 2.0 ** 127]
+    if fmt == "f16":
+        assert np.isnan(sp.decode(fmt, np.array([0x7E00], dtype=np.uint16).view(np.float16))[0])
+
+
+@pytest.mark.parametrize("fmt", sp.FORMATS)
+def test_value_sweeps_change_one_element_a_line_and_no_launch_is_vacuous(fmt):
+    m, n, k = SWEEP
+    hac, hmeta, hbt = sp.fill(fmt, m, n, k)
+    expect = sp.expected(fmt, m, n, k)
+    assert np.array_equal(sp.product(hac, hmeta, hbt), expect)
+    for side, clean in ((0, hac), (1, hbt)):
+        wrong = sp.sweep_values(fmt, clean, side)
+        x = np.arange(clean.shape[0])
+        assert np.array_equal(np.argwhere(wrong != clean), np.stack([x, x % clean.shape[1]], axis=1))
+        mul = sp.MUL[fmt][side]
+        assert set(np.unique(wrong[x, x % clean.shape[1]] // mul).tolist()) == {1, 2} and not (wrong % mul).any()
+        assert np.array_equal(sp.decode(fmt, sp.encode(fmt, wrong)), wrong)  # values of the format
+        ops = (wrong, hmeta, hbt) if side == 0 else (hac, hmeta, wrong)
+        assert (np.abs(sp.decompress(ops[0], hmeta)) @ np.abs(ops[2]).T).max() < sp.EXACT_BELOW[fmt]
+        mismatch = sp.product(*ops) != expect
+        lines = mismatch if side == 0 else mismatch.T
+        # launch x has element x alone: its line x is line x of this product, every other line is clean
+        counts = lines.sum(axis=1)
+        assert (counts.min(), counts.max()) == ((438, 439) if side == 0 else (204, 206))
+        one = clean.copy()
+        one[300, 300 % clean.shape[1]] = wrong[300, 300 % clean.shape[1]]
+        alone = sp.product(*((one, hmeta, hbt) if side == 0 else (hac, hmeta, one))) != expect
+        alone = alone if side == 0 else alone.T
+        assert np.array_equal(alone[300], lines[300]) and not np.delete(alone, 300, axis=0).any()
+    # a changed B element is wrong only in the rows that keep its k with a non-zero value
+    dense = sp.decompress(hac, hmeta)
+    wrong = sp.sweep_values(fmt, hbt, 1)
+    mismatch = sp.product(hac, hmeta, wrong) != expect
+    for j in (0, 77, 511):
+        assert np.array_equal(mismatch[:, j], dense[:, j % k] != 0)
+    # the slots of the A sweep are every place of the kernel's operand feed
+    stages = k // sp.STAGE[fmt]
+    places = set(zip(*(np.asarray(c).tolist() for c in sp.kept_slot_coordinates(fmt, np.arange(m) % (k // 2)))))
+    assert len(places) == k // 2 == stages * 2 * 2 * (8 // sp.ESIZE[fmt]) * 2
+    assert sp.kept_slot_coordinates("bf16", 319) == (9, 1, 1, 3, 1) and sp.kept_slot_coordinates("i8", 319) == (4, 1, 1, 7, 1)
+    assert sp.kept_slot_coordinates("f16", 8) == (0, 0, 1, 0, 0) and sp.kept_slot_coordinates("fp8", 32) == (0, 1, 0, 0, 0)
+
+
+def test_nibble_plan_covers_every_group_nibble_and_byte_half():
+    m, n, k = SWEEP
+    group, new, moved = sp.nibble_sweep_plan(m, n, k)
+    assert set(group.tolist()) == set(range(k // 4)) and set(new.tolist()) == set(sp.VALID_NIBBLES)
+    assert set((group % 2).tolist()) == {0, 1} and 0 < moved < m // 4
+    # it starts at group i mod (K/4) and rarely moves to the next group
+    assert (((group - np.arange(m)) % (k // 4)) <= 1).all()
+    for fmt in sp.FORMATS:
+        hac, hmeta, hbt = sp.fill(fmt, m, n, k)
+        wrong = sp.meta_with_nibbles(hmeta, group, new)
+        assert np.array_equal(np.argwhere(wrong != hmeta), np.stack([np.arange(m), group // 2], axis=1))
+        was, now = sp.unpack_meta(hmeta), sp.unpack_meta(wrong)
+        assert np.array_equal(np.argwhere(was != now), np.stack([np.arange(m), group], axis=1))  # the one nibble
+        mismatch = sp.product(hac, wrong, hbt) != sp.expected(fmt, m, n, k)
+        counts = mismatch.sum(axis=1)
+        assert counts.min() > 0 and counts.max() <= n, fmt  # no launch is vacuous
+        assert np.array_equal(sp.product_per_slot(hac, now, hbt), sp.product(hac, wrong, hbt))
+    print("nibble plan:", moved, "rows moved on; mismatches a launch", counts.min(), "..", counts.max())
+
+
+def test_per_slot_product_in_float64_multiplies_only_what_a_row_keeps():
+    m, n, k = 60, 14, 128
+    for fmt in ("f16", "bf8"):
+        hac, hmeta, hbt = sp.fill(fmt, m, n, k)
+        nib = sp.unpack_meta(hmeta)
+        clean = sp.product_per_slot_f64(hac, nib, hbt)
+        assert clean.dtype == np.float64 and np.array_equal(clean, sp.expected(fmt, m, n, k))
+        keep = sp.keep_mask(m, k)
+        for bad in (np.nan, np.inf):
+            j, kk = 9, 77
+            b = hbt.astype(np.float64)
+            b[j, kk] = bad
+            got = sp.product_per_slot_f64(hac, nib, b)
+            assert np.array_equal(np.isnan(got) | np.isinf(got), np.outer(keep[:, kk], np.arange(n) == j))
+            kept_zero = keep[:, kk] & (sp.decompress(hac, hmeta)[:, kk] == 0)
+            assert kept_zero.any() and np.isnan(got[kept_zero, j]).all()  # 0 · inf and 0 · NaN
+            i, slot = 31, 40
+            a = hac.astype(np.float64)
+            a[i, slot] = bad
+            got = sp.product_per_slot_f64(a, nib, hbt)
+            assert not np.isfinite(got[i]).any() and np.array_equal(np.delete(got, i, axis=0), np.delete(clean, i, axis=0))
+
+
+@pytest.mark.parametrize("fmt,swap", [(f, False) for f in sp.FORMATS] + [("bf16", True)])
+def test_onehot_case_is_one_exact_product_per_output(fmt, swap):
+    ac, meta, bt, want = sp.onehot_case(fmt, swap)
+    stage = sp.STAGE[fmt]
+    assert ac.shape == (256, stage // 2) and meta.shape == (256, stage // 8) and bt.shape == (256, stage)
+    assert ac.dtype == bt.dtype == sp.NP_STORED[fmt] and meta.dtype == np.uint8 and want.shape == (256, 256)
+    nib = sp.unpack_meta(meta)
+    assert set(np.unique(nib).tolist()) == set(sp.VALID_NIBBLES)
+    rows, cols = sp.store_values(fmt, swap)
+    i = np.arange(256)
+    raw = ac.view(np.uint8).reshape(256, stage // 2, -1).any(axis=2)  # by bits: -0 and NaN are elements too
+    hot = i % (stage // 2)
+    assert not (raw & (np.arange(stage // 2)[None, :] != hot[:, None])).any()  # +0 everywhere else
+    assert np.array_equal(ac[i, hot].view(np.uint8), np.ascontiguousarray(rows).view(np.uint8))
+    assert set(hot.tolist()) == set(range(stage // 2))  # every kept slot of the stage
+    assert (bt.view(np.uint8).reshape(256, stage, -1) == bt.view(np.uint8).reshape(256, stage, -1)[:, :1]).all()
+    va, vb = sp.decode(fmt, rows), sp.decode(fmt, cols)
+    if fmt in ("fp8", "bf8", "i8"):  # every pair of codes / values
+        assert sorted(np.asarray(rows).view(np.uint8).tolist()) == sorted(np.asarray(cols).view(np.uint8).tolist()) == list(range(256))
+    finite = np.isfinite(want)
+    with np.errstate(invalid="ignore"):
+        single = va[:, None] * vb[None, :]
+    # where the model is finite it is the one product, and the same product summed with the row's zeros
+    # through the float64 per-slot model, whatever the nibbles select
+    assert np.array_equal(want[finite], single[finite])
+    full = sp.product_per_slot_f64(sp.decode(fmt, ac), nib, sp.decode(fmt, bt))
+    assert np.array_equal(np.isnan(full), np.isnan(want)) and np.array_equal(full[~np.isnan(want)], want[~np.isnan(want)])
+    # exact in the accumulator: fp32 holds every finite product (int32 every i8 one)
+    if fmt == "i8":
+        assert finite.all() and np.abs(want).max() == 128 * 128
+    else:
+        assert np.array_equal(want[finite].astype(np.float32).astype(np.float64), want[finite])
+        nz = finite & (want != 0)
+        assert np.abs(want[nz]).min() >= 2.0 ** -126  # normal fp32 numbers
+    if fmt == "fp8":
+        assert np.isnan(want).sum() == 2 * 256 + 2 * 254 and not np.isinf(want).any()
+        assert want[0x7E, 0x7E] == 448.0 * 448.0 and want[1, 1] == 2.0 ** -18
+    if fmt == "bf8":
+        assert np.isnan(want[:, [0x7C, 0xFC, 0x7D, 0xFF]]).all()  # an infinite or NaN column value: 0 · inf
+        assert want[0x7C, 0x3C] == np.inf and want[0x7C, 0xBC] == -np.inf and np.isnan(want[0x7C, 0]) and np.isnan(want[0x7E, 0x3C])
+        assert want[0x7B, 0x7B] == 57344.0 ** 2 and want[1, 1] == 2.0 ** -32
+    if fmt in ("f16", "bf16"):
+        assert finite.all()
+    if fmt == "bf16":
+        big, small = (sp.decode("bf16", x.view(np.int16)) for x in sp.bf16_value_sets())
+        assert np.array_equal(va, small if swap else big) and np.array_equal(vb, big if swap else small)
+        assert set(range(-8, 9)) <= set(big.tolist()) and {(2 - 2.0 ** -7) * 2.0 ** 127, -(2 - 2.0 ** -7) * 2.0 ** 127} <= set(big.tolist())
+        assert 2.0 ** -126 in small.tolist() and np.signbit(big[big == 0]).any() and np.signbit(small[small == 0]).any()
+        assert np.abs(big[big != 0]).min() >= 1 and np.abs(small[small != 0]).max() < 0.5 and np.abs(small[small != 0]).min() == 2.0 ** -126
+        ones = lambda v: (v.view(np.uint16) & 0x7F) == 0x7F  # noqa: E731
+        assert ones(sp.bf16_value_sets()[0]).sum() >= 127 and ones(sp.bf16_value_sets()[1]).sum() >= 125
+    if fmt == "f16":
+        assert np.array_equal(want, ref.f16_onehot_case()[2])
