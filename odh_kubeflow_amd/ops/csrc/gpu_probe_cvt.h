@@ -41,9 +41,20 @@
 // shared exponent floor(log2(amax)) - emax of the element format clamped to the E8M0 range, 2^0 for an
 // all-zero block, and OCP saturation (clamped in f32 before the conversion, so the contract does not
 // depend on what the instruction does beyond the largest finite value).  Not QUANT: the caller's scales
-// and the bare instruction.  A streaming kernel on the slabs of the HBM sweep: 16-byte loads, four in
-// flight per lane, eight lanes to a block of 32 with amax by three cross-lane steps; the 6-bit formats
-// take a block per lane, because their one instruction wants all 32 values in one lane.
+// and the bare instruction.  QUANT's contract for every f32, per block of 32 (tests/cvt_reference.py is its
+// model, tests/test_gpu_cvt_edges.py holds the kernel to it):
+//   - amax is the largest |x| over the elements that are not NaN; +-Inf counts as FLT_MAX;
+//   - if no such element exists, or all are zero, the byte is 127;
+//   - otherwise byte = clamp(floor(log2 amax) - emax + 127, 0, 254); with an Inf in the block that is
+//     254 - emax.  Byte 255 (the E8M0 NaN) is never emitted;
+//   - finite elements are clamped in f32 to +-(largest finite value · scale) and then converted;
+//   - +-Inf becomes the largest finite code with its sign, in every format: the saturation of finite overflow;
+//   - NaN goes to the instruction unclamped: fp8 0xFF and bf8 0xFE whatever the sign; fp4, fp6 and bf6 have no
+//     NaN and give their largest code with the input's sign, so these three formats cannot carry a NaN.
+// bf16 is the plain conversion: Inf stays Inf, NaN stays NaN, quieted.
+// A streaming kernel on the slabs of the HBM sweep: 16-byte loads, four in flight per lane, eight lanes to
+// a block of 32 with amax by three cross-lane steps; the 6-bit formats take a block per lane, because
+// their one instruction wants all 32 values in one lane.
 
 typedef __attribute__((ext_vector_type(2))) short i16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -271,11 +282,19 @@ __global__ __launch_bounds__(256, 1) void cvt_probe_kernel(const uint8_t* __rest
   }
 }
 
-// the OCP MX scale of a block: floor(log2(amax)) - emax as an E8M0 byte, clamped; 2^0 for amax = 0.  The
-// exponent field of a subnormal amax is 0, which clamps to byte 0 as its true exponent would
-__device__ __forceinline__ unsigned cvt_mx_scale(float amax, int emax) {
-  if (amax == 0.f) return 127u;
-  const int b = (int)(__float_as_uint(amax) >> 23 & 0xFFu) - emax;
+// The running amax of a block, on the bits: among f32 that are not NaN the magnitude's bits order as the
+// values do.  A NaN counts as 0, whatever it is: fmaxf would drop a quiet one but returns a NaN for a
+// signalling one, and with it loses what it had seen before
+__device__ __forceinline__ uint32_t cvt_amax(uint32_t amax, float x) {
+  const uint32_t m = __float_as_uint(x) & 0x7FFFFFFFu;
+  return max(amax, m > 0x7F800000u ? 0u : m);
+}
+// the OCP MX scale of a block from amax's bits: floor(log2(amax)) - emax as an E8M0 byte, clamped; 2^0 for
+// amax = 0.  An infinite amax counts as FLT_MAX, so the byte is at most 254 - emax.  The exponent field of a
+// subnormal amax is 0, which clamps to byte 0 as its true exponent would
+__device__ __forceinline__ unsigned cvt_mx_scale(uint32_t amax, int emax) {
+  if (amax == 0u) return 127u;
+  const int b = (int)(min(amax, 0x7F7FFFFFu) >> 23) - emax;
   return (unsigned)(b < 0 ? 0 : b > 254 ? 254 : b);
 }
 // the largest finite value of the format times the scale, as an f32 no larger than FLT_MAX
@@ -284,7 +303,8 @@ __device__ __forceinline__ float cvt_limit(CvtSpec s, unsigned byte) {
   const unsigned m = (unsigned)cvt_m(s, s.cmax);
   return 127 + cvt_ilog2(m) + sh > 254 ? 3.402823466e38f : __uint_as_float(cvt_fbits(m, sh));
 }
-__device__ __forceinline__ float cvt_clamp(float x, float lim) { return fminf(fmaxf(x, -lim), lim); }
+// a NaN passes: the instruction turns it into the format's NaN, or the largest code where there is none
+__device__ __forceinline__ float cvt_clamp(float x, float lim) { return x != x ? x : fminf(fmaxf(x, -lim), lim); }
 
 // x [n / 8 blocks of 32] to codes and scales; n counts 16-byte pieces of x (6-bit formats: blocks)
 template <int FMT, bool QUANT>
@@ -304,9 +324,9 @@ __global__ __launch_bounds__(256) void cvt_rows_kernel(const cvt_f4* __restrict_
       for (int u = 0; u < 8; ++u) e[4 * u] = v[u].x, e[4 * u + 1] = v[u].y, e[4 * u + 2] = v[u].z, e[4 * u + 3] = v[u].w;
       unsigned byte;
       if (QUANT) {
-        float amax = 0.f;
+        uint32_t amax = 0u;
 #pragma unroll
-        for (int k = 0; k < 32; ++k) amax = fmaxf(amax, fabsf(e[k]));
+        for (int k = 0; k < 32; ++k) amax = cvt_amax(amax, e[k]);
         byte = cvt_mx_scale(amax, S.emax);
         scales_out[blk] = (uint8_t)byte;
         const float lim = cvt_limit(S, byte);
@@ -339,9 +359,9 @@ __global__ __launch_bounds__(256) void cvt_rows_kernel(const cvt_f4* __restrict_
           const size_t blk = i >> 3;
           unsigned byte;
           if (QUANT) {
-            float amax = fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fmaxf(fabsf(w.z), fabsf(w.w)));
+            uint32_t amax = cvt_amax(cvt_amax(cvt_amax(cvt_amax(0u, w.x), w.y), w.z), w.w);
 #pragma unroll
-            for (int off = 1; off < 8; off <<= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+            for (int off = 1; off < 8; off <<= 1) amax = max(amax, __shfl_xor(amax, off, 64));
             byte = cvt_mx_scale(amax, S.emax);
             if ((i & 7) == 0) scales_out[blk] = (uint8_t)byte;
             const float lim = cvt_limit(S, byte);

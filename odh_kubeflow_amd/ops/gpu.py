@@ -949,7 +949,20 @@ def mx_quantize(fmt, x):
     """OCP MX quantisation on the GPU: ``x`` ``[rows, K]`` float32 to ``(codes, scales)`` as :func:`mx_gemm`
     takes them.  The scale of a block of 32 is ``2^(floor(log2(amax)) - emax)`` of the element format, clamped
     to E8M0 (2^0 for an all-zero block); the elements go through the hardware converter with that scale and
-    saturate at the largest finite code.  ``"bf16"`` is the plain conversion: ``(bfloat16 tensor, None)``."""
+    saturate at the largest finite code.  ``"bf16"`` is the plain conversion: ``(bfloat16 tensor, None)``.
+
+    Any float32 may come in.  For the scaled formats, per block of 32:
+
+    * amax is the largest ``|x|`` over the elements that are not NaN; ±Inf counts as FLT_MAX.
+    * If no such element exists, or all are zero, the scale byte is 127.
+    * Otherwise the byte is ``clamp(floor(log2 amax) - emax + 127, 0, 254)``; with an Inf in the block that
+      is ``254 - emax``.  Byte 255 (the E8M0 NaN) is never emitted.
+    * Finite elements are clamped in float32 to ±(largest finite value · scale) and then converted.
+    * ±Inf becomes the largest finite code with its sign, in every format, like finite overflow.
+    * NaN becomes the format's NaN, fp8 0xFF and bf8 0xFE, whatever its sign.  fp4, fp6 and bf6 have no NaN:
+      there a NaN becomes the largest code with the input's sign, so these three formats cannot carry a NaN.
+
+    bf16: Inf stays Inf and NaN stays NaN, quieted."""
     import torch
 
     code, rows, k = _cvt_rows(fmt, x)

@@ -2934,7 +2934,9 @@ const char* reason_phrase(int code) {
 // kube-apiserver's --audit-log-path / --audit-policy-file for debugging test runs (the
 // reference's envtest DEBUG_WRITE_AUDITLOG, odh/controllers/suite_test.go:125-137); the
 // policy subset and event shape match apiserver/audit.py.  One JSON line per request at
-// ResponseComplete (watches: ResponseStarted), written under a mutex.
+// ResponseComplete (watches: ResponseStarted), written under a mutex, and, as in apiserver/http.py,
+// before the response goes out: a client that sends its next request when it has the answer to the
+// last finds the two lines in that order, whichever threads serve them.
 
 struct Audit {
   bool on = false;
@@ -2950,6 +2952,7 @@ struct AuditCtx {
   std::string level, verb, group, version, resource, ns, name, sub, received;
   int code = 0;
   std::string resp;  // response body (RequestResponse only)
+  const std::string *uri = nullptr, *ua = nullptr, *body = nullptr;  // of the request being served
 };
 thread_local AuditCtx t_aud;
 
@@ -3115,6 +3118,9 @@ bool respond(int fd, int code, std::string_view body, bool keep_alive) {
       } catch (const kj::ParseError&) {
       }
     }
+    audit_write(t_aud, *t_aud.uri, *t_aud.ua, *t_aud.body, "ResponseComplete");  // before the send
+    t_aud.on = false;
+    t_aud.resp.clear();
   }
   book_request();
   char h[160];
@@ -3943,6 +3949,7 @@ bool handle(int fd, Request& rq) {
         t_aud.received = micro_now();
         t_aud.code = 200;
         t_aud.resp.clear();
+        t_aud.uri = &rq.target, t_aud.ua = &rq.user_agent, t_aud.body = &rq.body;
         if (watch) {  // a stream: logged when it starts
           audit_write(t_aud, rq.target, rq.user_agent, "", "ResponseStarted");
           t_aud.on = false;

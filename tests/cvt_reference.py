@@ -11,6 +11,21 @@ calling the library:
 * :func:`family` — the input family of the fused check with its expected codes *by construction*: no
   rounding happens in it.  :func:`encode` applied to its inputs must give its expectations.
 * :func:`quantize` — the public operation: OCP MX scales and saturating codes, in the layout ``mx_gemm`` reads.
+
+The contract of the public operation for every f32, non-finite ones included (the same words as in
+``gpu_probe_cvt.h`` and ``gpu.mx_quantize``).  For the scaled formats, per block of 32:
+
+* amax is the largest ``|x|`` over the elements that are not NaN; ±Inf counts as FLT_MAX.
+* If no such element exists, or all are zero, the scale byte is 127.
+* Otherwise the byte is ``clamp(floor(log2 amax) - emax + 127, 0, 254)``; with an Inf in the block that is
+  ``254 - emax``.  Byte 255 is never emitted.
+* Finite elements are clamped in f32 to ±(largest finite value · scale) and then converted.
+* ±Inf becomes the largest finite code with its sign, in every format: the saturation of finite overflow.
+* NaN goes to the instruction unclamped and becomes what :data:`NAN_CODE` records: fp8 0xFF and bf8 0xFE
+  whatever the sign; fp4, fp6 and bf6 have no NaN and give their largest code with the input's sign, so these
+  three formats cannot carry a NaN.
+
+bf16 is the plain conversion: Inf stays Inf, NaN stays NaN, quieted.
 """
 
 import numpy as np
@@ -29,6 +44,12 @@ OVERFLOW = {FP8: (126, 0x7F), BF8: (0x7C, 0x7C), FP4: (7, 7), FP6: (31, 31), BF6
 # of a NaN input (outside the probe's family), whatever its sign; the other formats give their largest code
 # with the input's sign
 NAN_CODE = {FP8: 0xFF, BF8: 0xFE}
+# of any input, zero included, at scale byte 255 (the E8M0 NaN), as recorded from the hardware: what a NaN
+# input gives.  The format's NaN whatever the input's sign, or the largest code with the input's sign (the
+# magnitude code here; an earlier single measurement had taken it for the positive code).  The quantiser
+# never emits that byte
+SCALE_NAN_CODE = {FP8: 0xFF, BF8: 0xFE, FP4: 7, FP6: 31, BF6: 31}
+FLT_MAX = float(np.finfo(np.float32).max)
 BF16_EXPS = 254
 
 
@@ -53,7 +74,8 @@ def overflow_midpoint(fmt):
 
 
 def encode(fmt, x, scale_bytes=127):
-    """Codes (one per element, sign included, not packed) of f32 ``x`` divided by ``2^(scale_bytes - 127)``."""
+    """Codes (one per element, sign included, not packed) of f32 ``x`` divided by ``2^(scale_bytes - 127)``;
+    at scale byte 255 :data:`SCALE_NAN_CODE`, with the input's sign where the format has no NaN."""
     x = np.asarray(x, dtype=np.float32)
     if fmt == BF16:
         bits = x.view(np.uint32).astype(np.uint64)
@@ -78,7 +100,9 @@ def encode(fmt, x, scale_bytes=127):
     code = np.where(ys < mid, np.minimum(code, CMAX[fmt]), np.where(ys == mid, tie, beyond))
     code = np.where(np.isinf(y), beyond, code)
     code = np.where(np.isnan(y), CMAX[fmt], code) | (neg.astype(np.int64) << sign_bit(fmt))
-    return np.where(np.isnan(y), NAN_CODE[fmt], code) if fmt in NAN_CODE else code
+    code = np.where(np.isnan(y), NAN_CODE[fmt], code) if fmt in NAN_CODE else code
+    signed = 0 if fmt in NAN_CODE else neg.astype(np.int64) << sign_bit(fmt)
+    return np.where(sb == 255, SCALE_NAN_CODE[fmt] | signed, code)
 
 
 # ------------------------------------------------------------------ the family of the fused check
@@ -158,23 +182,28 @@ def family(fmt):
 
 def mx_scales(fmt, x):
     """OCP MX: per block of 32 along the last axis, ``floor(log2(amax)) - emax`` as an E8M0 byte clamped to
-    0 … 254; the byte of 2^0 for an all-zero block."""
+    0 … 254, amax over the elements that are not NaN with ±Inf counted as FLT_MAX; the byte of 2^0 for a block
+    that is all zero or has nothing but NaN."""
     x = np.asarray(x, dtype=np.float32)
-    amax = np.abs(x.astype(np.float64)).reshape(*x.shape[:-1], -1, 32).max(axis=-1)
+    mag = np.abs(x.astype(np.float64))
+    mag = np.where(np.isnan(mag), 0.0, np.minimum(mag, FLT_MAX))
+    amax = mag.reshape(*x.shape[:-1], -1, 32).max(axis=-1)
     _, ex = np.frexp(amax)
     byte = np.clip(ex - 1 - emax(fmt) + 127, 0, 254)
     return np.where(amax == 0, 127, byte).astype(np.uint8)
 
 
 def quantize(fmt, x):
-    """``(codes, scales)`` of f32 ``x`` ``[rows, K]``: the public layout of ``mx_gemm``; saturating.  bf16:
+    """``(codes, scales)`` of f32 ``x`` ``[rows, K]``: the public layout of ``mx_gemm``; saturating, ±Inf
+    included; a NaN stays one where the format has one (the module's docstring).  bf16:
     ``(uint16 bits [rows, K], None)``."""
     x = np.asarray(x, dtype=np.float32)
     if fmt == BF16:
         return encode(BF16, x).astype(np.uint16), None
     scales = mx_scales(fmt, x)
     per = np.repeat(scales.astype(np.int64), 32, axis=-1)
-    lim = magnitudes(fmt)[-1] * 2.0 ** (per - 127).astype(np.float64)
-    clamped = np.clip(x.astype(np.float64), -lim, lim)
-    clamped = np.minimum(np.abs(clamped), np.finfo(np.float32).max) * np.where(np.signbit(x), -1.0, 1.0)
-    return mx.pack(fmt, encode(fmt, clamped.astype(np.float32), per).astype(np.uint8)), scales
+    lim = np.minimum(magnitudes(fmt)[-1] * 2.0 ** (per - 127).astype(np.float64), FLT_MAX)
+    assert (lim.astype(np.float32).astype(np.float64) == lim).all()  # the clamp happens in f32
+    clamped = np.clip(x.astype(np.float64), -lim, lim)  # np.clip keeps a NaN
+    with np.errstate(invalid="ignore"):
+        return mx.pack(fmt, encode(fmt, clamped.astype(np.float32), per).astype(np.uint8)), scales

@@ -7,13 +7,15 @@
 * the family of the fused check: ``odh_cvt_family`` of the built library against the host model
   (``cvt_reference.py``) bit for bit, its expectations against the model's encoder applied independently
   to its inputs, and what it covers;
-* the host model of the quantiser: round trip, the scale rule, saturation, the all-zero block.
+* the host model of the quantiser: round trip, the scale rule, saturation, the all-zero block, and its
+  contract for non-finite and subnormal input against a scalar reimplementation, block by block.
 """
 
 from __future__ import annotations
 
 import itertools
 import json
+import math
 import os
 import re
 import subprocess
@@ -392,6 +394,159 @@ def test_quantize_scale_rule_saturation_and_zero_blocks(fmt):
     raw = cr.encode(fmt, np.float32(1.99 * 2.0 ** em))
     assert int(raw) == cr.OVERFLOW[fmt][1]
     assert cr.mx_scales(fmt, np.full((1, 32), 3e38, dtype=np.float32))[0, 0] == 127 + 127 - em  # no clamp needed above
+
+
+def _contract_block(fmt, block):
+    """One block of 32 by the contract's sentences (``gpu.mx_quantize``), element by element in Python floats:
+    ``(byte, codes)``.  Only a finite, already clamped element goes through the model's encoder."""
+    em, top, cmax, sign = cr.emax(fmt), float(cr.magnitudes(fmt)[-1]), cr.CMAX[fmt], cr.sign_bit(fmt)
+    flt_max = float(np.finfo(np.float32).max)
+    block = [float(v) for v in block]
+    counted = [min(abs(v), flt_max) for v in block if not math.isnan(v)]  # ±Inf counts as FLT_MAX
+    amax = max(counted, default=0.0)
+    if amax == 0:  # nothing but NaN, or all zero
+        byte = 127
+    else:
+        byte = min(max(math.frexp(amax)[1] - 1 - em + 127, 0), 254)  # amax = m · 2^e, 0.5 <= m < 1
+    lim = top * 2.0 ** (byte - 127)
+    codes = []
+    for v in block:
+        neg = math.copysign(1.0, v) < 0
+        if math.isnan(v):
+            codes.append(cr.NAN_CODE[fmt] if fmt in cr.NAN_CODE else cmax | neg << sign)
+        elif math.isinf(v):
+            codes.append(cmax | neg << sign)
+        else:
+            c = np.float32(min(max(v, -lim), lim))
+            assert float(c) == min(max(v, -lim), lim)  # the clamp is exact in f32
+            codes.append(int(cr.encode(fmt, c, byte)))
+    return byte, codes
+
+
+def _f32(bits):
+    return np.array(bits, dtype=np.uint32).view(np.float32)
+
+
+def _edge_blocks():
+    """Blocks of 32 f32 around every sentence of the contract, and seeded ones with non-finite elements."""
+    rng = np.random.default_rng(321)
+    inf, nan, flt_max, tiny = np.float32(np.inf), np.float32(np.nan), np.finfo(np.float32).max, np.float32(2.0 ** -149)
+    snan, qnan_neg = _f32(0x7F800001), _f32(0xFFC00000)
+    base = (rng.standard_normal(32) * 8).astype(np.float32)
+    blocks = []
+
+    def put(**at):
+        b = base.copy()
+        for k, v in at.items():
+            b[int(k[1:])] = v
+        blocks.append(b)
+
+    blocks.append(np.zeros(32, dtype=np.float32))
+    blocks.append(np.full(32, nan))
+    blocks.append(np.full(32, -0.0, dtype=np.float32))
+    for v in (inf, -inf):
+        b = np.zeros(32, dtype=np.float32)
+        b[7] = v
+        blocks.append(b)
+        put(p3=v)
+        put(p3=v, p9=flt_max, p10=-flt_max)
+    for v in (nan, -nan, snan, -snan, qnan_neg):
+        put(p0=v)
+        put(p31=v, p4=inf)
+        b = np.zeros(32, dtype=np.float32)
+        b[11] = v
+        blocks.append(b)  # a NaN and zeros: byte 127
+    b = np.full(32, nan)
+    b[::3] = inf
+    b[1::6] = -inf
+    blocks.append(b)  # NaN and Inf only
+    blocks.append(np.full(32, flt_max))
+    blocks.append(np.full(32, tiny))  # the smallest subnormal: byte 0
+    for e in (-149, -140, -127, -126, -120, -112, -105, 100, 120, 127):
+        b = (base * np.float32(2.0 ** -5)).astype(np.float64) * 2.0 ** e
+        with np.errstate(over="ignore", under="ignore"):
+            blocks.append(np.clip(b, -flt_max, flt_max).astype(np.float32))
+    for _ in range(40):  # seeded bit patterns: every exponent field, 255 included
+        b = rng.integers(0, 1 << 32, 32, dtype=np.uint64).astype(np.uint32).view(np.float32).copy()
+        blocks.append(b)
+        b = (b.view(np.uint32) & 0x83FFFFFF | 0x3C000000).view(np.float32).copy()  # a narrow range
+        b[rng.integers(0, 32)] = rng.choice([inf, -inf, nan, snan])
+        blocks.append(b)
+    return np.stack(blocks)
+
+
+@pytest.mark.parametrize("fmt", cr.SCALED)
+def test_quantize_is_the_contract_block_by_block(fmt):
+    x = _edge_blocks()
+    assert np.isnan(x).any() and np.isinf(x).any() and len(x) > 100
+    with np.errstate(invalid="ignore"):
+        q, s = cr.quantize(fmt, x)
+        codes = mx.unpack(fmt, q)
+    assert s.shape == (len(x), 1) and codes.shape == x.shape
+    for i, block in enumerate(x):
+        byte, want = _contract_block(fmt, block)
+        assert int(s[i, 0]) == byte, (i, block)
+        assert codes[i].tolist() == want, (i, block)
+    # reshaped to three blocks a row the blocks are the same blocks
+    n = len(x) // 3 * 3
+    with np.errstate(invalid="ignore"):
+        q3, s3 = cr.quantize(fmt, x[:n].reshape(-1, 96))
+    assert np.array_equal(s3.reshape(-1), s[:n, 0]) and np.array_equal(mx.unpack(fmt, q3).reshape(-1, 32), codes[:n])
+    assert s.max() == 254 - cr.emax(fmt) and s.min() == 0 and (s != 255).all()
+
+
+@pytest.mark.parametrize("fmt", cr.SCALED)
+def test_quantize_contract_of_non_finite_elements(fmt):
+    """The contract's sentences one by one, as numbers."""
+    em, cmax, sign = cr.emax(fmt), cr.CMAX[fmt], 1 << cr.sign_bit(fmt)
+    nan_pos, nan_neg = (cr.NAN_CODE[fmt],) * 2 if fmt in cr.NAN_CODE else (cmax, cmax | sign)
+    x = np.zeros((6, 32), dtype=np.float32)
+    x[0, 4] = np.inf  # alone among zeros
+    x[1] = np.linspace(-3, 3, 32)
+    x[1, 2], x[1, 20] = -np.inf, np.finfo(np.float32).max  # among finite values, FLT_MAX one of them
+    x[2] = x[3] = np.linspace(-3, 3, 32)
+    x[2, 6], x[2, 9] = _f32(0x7F800001), _f32(0xFFC00000)  # NaN of both signs among finite values
+    x[3, 6], x[3, 9] = 0, 0  # the same block without them
+    x[4] = np.nan
+    x[5, ::2], x[5, 1::2] = np.nan, -np.inf
+    with np.errstate(invalid="ignore"):
+        q, s = cr.quantize(fmt, x)
+        c = mx.unpack(fmt, q).astype(np.int64)
+    assert s[:, 0].tolist() == [254 - em, 254 - em, s[3, 0], s[3, 0], 127, 254 - em] and s[3, 0] == 127 + 1 - em
+    assert c[0, 4] == cmax and not np.delete(c[0], 4).any()
+    assert c[1, 2] == cmax | sign and c[1, 20] == cmax  # Inf and FLT_MAX saturate alike
+    assert set(np.delete(c[1], [2, 20]).tolist()) <= {0, sign}  # 3 / 2^(127 - emax) is far below half a step
+    assert c[2, 6] == nan_pos and c[2, 9] == nan_neg
+    assert np.array_equal(np.delete(c[2], [6, 9]), np.delete(c[3], [6, 9]))  # the finite neighbours are unchanged
+    assert (c[4] == nan_pos).all()
+    assert (c[5, ::2] == nan_pos).all() and (c[5, 1::2] == (cmax | sign)).all()
+    # what the encoder records beside it
+    assert int(cr.encode(fmt, np.float32(np.inf), 127)) == cr.OVERFLOW[fmt][1]  # the bare instruction does not saturate
+    every = (np.arange(65536, dtype=np.uint32) << 16).view(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        at255 = cr.encode(fmt, every, 255)
+    assert (at255 == cr.SCALE_NAN_CODE[fmt] | (0 if fmt in cr.NAN_CODE else np.signbit(every) * sign)).all()
+    assert np.array_equal(at255, cr.encode(fmt, np.where(np.signbit(every), -np.float32(np.nan), np.float32(np.nan))))
+    assert cr.SCALE_NAN_CODE[fmt] == (cr.NAN_CODE[fmt] if fmt in cr.NAN_CODE else cmax)
+
+
+def test_f32_subnormal_inputs_at_the_smallest_scales():
+    """An f32 subnormal is not zero to the converter at scale bytes 0 and 1: 2^-127 / 2^-126 is 0.5."""
+    x = np.float32(2.0 ** -127)
+    assert int(cr.encode(cr.FP8, x, 1)) == 0x30 and int(cr.encode(cr.FP8, -x, 0)) == 0x38 | 0x80
+    assert int(cr.encode(cr.FP4, x, 1)) == 1 and int(cr.encode(cr.FP4, x, 0)) == 2
+    assert int(cr.encode(cr.FP8, x, 20)) == 0  # and below half the smallest subnormal from there on
+
+
+def test_bf16_model_keeps_inf_and_quiets_nan():
+    x = _f32([0x7F800000, 0xFF800000, 0x7F800001, 0xFF80FFFF, 0x7FC00000, 0xFFFFFFFF, 0x7F7FFFFF, 0x7F7F7FFF,
+              0x00000001, 0x00008000, 0x00008001, 0x807FFFFF, 0x00018000])
+    want = [0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7FC0, 0xFFFF, 0x7F80, 0x7F7F, 0, 0, 1, 0x8080, 2]
+    assert cr.encode(cr.BF16, x).tolist() == want
+    got = torch.from_numpy(x.copy()).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    finite = np.isfinite(x)
+    assert np.array_equal(got[finite], np.array(want, dtype=np.uint16)[finite])  # torch agrees off the NaNs
+    assert np.isnan(x[2:6]).all() and all(w & 0x7FFF > 0x7F80 for w in want[2:6])
 
 
 def test_bf16_model_is_torchs():
