@@ -185,6 +185,7 @@ GPU_PROBE_FP_FORMATS = "f32,f64"  # formats of the fp step (annotation token "fp
 GPU_PROBE_SPARSE_FORMATS = "bf16,f16,i8,fp8,bf8"  # 2:4 structured-sparsity formats (annotation token "sparse")
 GPU_PROBE_CVT_FORMATS = "fp8,bf8,fp4,fp6,bf6,bf16"  # destination formats of the converter step (annotation token "cvt")
 GPU_PROBE_LDS_FORMATS = "mem,tr16,tr8,tr4,tr6,xlane"  # checks of the LDS step (annotation token "lds")
+GPU_PROBE_MFMA16_FORMATS = "bf16,f16,i8,fp8,fp4"  # formats of the 16×16 matrix-core step (annotation token "mfma16")
 
 
 GPU_PROBE_TOKENS = ("true", "rccl", "mx", "mxall", "dtypes", "false")
@@ -192,17 +193,18 @@ GPU_PROBE_MORE_TOKENS = ("fp",)  # tokens added since: accepted like the ones ab
 GPU_PROBE_SPARSE_TOKENS = ("sparse",)  # and since then (tests/test_probe_fp.py holds the tuple above to its value)
 GPU_PROBE_CVT_TOKENS = ("cvt",)  # and since then (tests/test_probe_sparse.py holds the three above together)
 GPU_PROBE_LDS_TOKENS = ("lds",)  # and since then (tests/test_probe_cvt.py holds the four above together)
+GPU_PROBE_MFMA16_TOKENS = ("mfma16",)  # and since then (tests/test_probe_lds.py holds the five above together)
 
 
 def gpu_probe_tokens(nb: dict) -> frozenset:
     """The ``amd.com/gpu-probe`` annotation as a set of tokens.  It is a comma list of ``true``,
-    ``rccl``, ``mx``, ``mxall``, ``dtypes``, ``fp``, ``sparse``, ``cvt``, ``lds`` and ``false``: every one but ``true`` and ``false``
+    ``rccl``, ``mx``, ``mxall``, ``dtypes``, ``fp``, ``sparse``, ``cvt``, ``lds``, ``mfma16`` and ``false``: every one but ``true`` and ``false``
     turns the probe on and adds its step, so ``"rccl,mx"`` runs both.  A value with an unknown token, or with
     ``false`` next to another token, is ignored as a whole (the empty set), like an unknown value."""
     v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
     tokens = frozenset(t.strip() for t in v.split(",")) if v else frozenset()
     known = GPU_PROBE_TOKENS + GPU_PROBE_MORE_TOKENS + GPU_PROBE_SPARSE_TOKENS + GPU_PROBE_CVT_TOKENS \
-        + GPU_PROBE_LDS_TOKENS
+        + GPU_PROBE_LDS_TOKENS + GPU_PROBE_MFMA16_TOKENS
     if not tokens <= frozenset(known) or ("false" in tokens and len(tokens) > 1):
         return frozenset()
     return tokens
@@ -210,7 +212,7 @@ def gpu_probe_tokens(nb: dict) -> frozenset:
 
 def gpu_probe_enabled(nb: dict, pod_spec: dict, env: Mapping[str, str] = os.environ) -> bool:
     """The MI355X start-up probe runs for notebooks that request ``amd.com/gpu`` when the
-    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, ``"dtypes"``, ``"fp"``, ``"sparse"``, ``"cvt"``, ``"lds"``, or a comma
+    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, ``"dtypes"``, ``"fp"``, ``"sparse"``, ``"cvt"``, ``"lds"``, ``"mfma16"``, or a comma
     list of them), or when the operator turned it on for every GPU notebook (``GPU_STARTUP_PROBE=true``)
     and the Notebook does not say ``"false"``.  Off by default (never on the
     reconcile path, opt-in)."""
@@ -273,9 +275,17 @@ def gpu_probe_lds(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
     return "lds" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_LDS", "false") == "true"
 
 
+def gpu_probe_mfma16(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
+    """Whether the probe also checks the 16×16 shapes of the matrix-core instructions
+    (``--mfma16 bf16,f16,i8,fp8,fp4``): ``mfma16`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_MFMA16=true`` for every
+    probed notebook."""
+    return "mfma16" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_MFMA16", "false") == "true"
+
+
 def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False,
                              mx: bool = False, dtypes: bool = False, mx_all: bool = False,
-                             fp: bool = False, sparse: bool = False, cvt: bool = False, lds: bool = False) -> dict:
+                             fp: bool = False, sparse: bool = False, cvt: bool = False, lds: bool = False,
+                             mfma16: bool = False) -> dict:
     """Init container that proves the pod's GPUs healthy before the notebook starts.
 
     ``odh-gpu-probe`` (``ops/csrc/probe_cli.cpp``, torch-free) runs the bf16 MFMA GEMM checked
@@ -286,7 +296,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
     ``--mx fp8,fp4,bf8,fp6,bf6``; ``dtypes``: plus the FP16 and INT8 GEMMs, ``--dtypes f16,i8``;
     ``fp``: plus the FP32 and FP64 GEMMs, ``--fp f32,f64``; ``sparse``: plus the 2:4 structured-sparsity GEMMs,
     ``--sparse bf16,f16,i8,fp8,bf8``; ``cvt``: plus the quantising converters, ``--cvt fp8,bf8,fp4,fp6,bf6,bf16``;
-    ``lds``: plus the LDS, its transposing reads and the lane exchanges, ``--lds mem,tr16,tr8,tr4,tr6,xlane``);
+    ``lds``: plus the LDS, its transposing reads and the lane exchanges, ``--lds mem,tr16,tr8,tr4,tr6,xlane``;
+    ``mfma16``: plus the GEMMs again on the 16×16 instruction shapes, ``--mfma16 bf16,f16,i8,fp8,fp4``);
     non-zero exit keeps the pod in Init, and its JSON verdict is the container's termination message.  It asks for the same
     ``amd.com/gpu`` count as the notebook: the kubelet device manager hands an init
     container's devices on to the app containers, so the GPUs probed are the GPUs the
@@ -307,6 +318,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
         args += ["--cvt", GPU_PROBE_CVT_FORMATS]
     if lds:  # after the --cvt arguments, for the same reason
         args += ["--lds", GPU_PROBE_LDS_FORMATS]
+    if mfma16:  # after the --lds arguments, for the same reason
+        args += ["--mfma16", GPU_PROBE_MFMA16_FORMATS]
     return {
         "name": GPU_PROBE_CONTAINER,
         "image": env.get("GPU_PROBE_IMAGE") or DEFAULT_GPU_PROBE_IMAGE,
@@ -330,7 +343,8 @@ def _gpu_probe(nb: dict, pod_spec: dict, env: Mapping[str, str]) -> None:
     inits.insert(0, gpu_probe_init_container(n, env, rccl=gpu_probe_rccl(nb, n, env), mx=gpu_probe_mx(nb, env),
                                              dtypes=gpu_probe_dtypes(nb, env), mx_all=gpu_probe_mx_all(nb, env),
                                              fp=gpu_probe_fp(nb, env), sparse=gpu_probe_sparse(nb, env),
-                                             cvt=gpu_probe_cvt(nb, env), lds=gpu_probe_lds(nb, env)))
+                                             cvt=gpu_probe_cvt(nb, env), lds=gpu_probe_lds(nb, env),
+                                             mfma16=gpu_probe_mfma16(nb, env)))
 
 
 def generate_statefulset(nb: dict, is_generate_name: bool, env: Mapping[str, str] = os.environ) -> dict:

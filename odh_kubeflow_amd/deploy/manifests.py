@@ -77,7 +77,7 @@ PARAMS_ENV = "USE_ISTIO=false\nISTIO_GATEWAY=kubeflow/kubeflow-gateway\nISTIO_HO
              "GPU_SHM_SIZE_PER_GPU=\nMULTI_GPU_ENV=\nGPU_DEVICE_GROUPS=\n" \
              "GPU_STARTUP_PROBE=false\nGPU_PROBE_RCCL=false\nGPU_PROBE_MX=false\nGPU_PROBE_DTYPES=false\n" \
              "GPU_PROBE_MX_ALL=false\nGPU_PROBE_FP=false\nGPU_PROBE_SPARSE=false\nGPU_PROBE_CVT=false\n" \
-             "GPU_PROBE_LDS=false\n"
+             "GPU_PROBE_LDS=false\nGPU_PROBE_MFMA16=false\n"
 # GPU_STARTUP_PROBE: the start-up probe for every GPU notebook (else opt-in per notebook,
 # amd.com/gpu-probe); GPU_PROBE_RCCL: its RCCL all-reduce for every probed multi-GPU notebook;
 # GPU_PROBE_MX: its FP8 / MXFP4 block-scaled GEMM checks for every probed notebook;
@@ -86,7 +86,8 @@ PARAMS_ENV = "USE_ISTIO=false\nISTIO_GATEWAY=kubeflow/kubeflow-gateway\nISTIO_HO
 # probed notebook; GPU_PROBE_FP: its FP32 / FP64 GEMM checks for every probed notebook;
 # GPU_PROBE_SPARSE: its 2:4 structured-sparsity GEMM checks for every probed notebook;
 # GPU_PROBE_CVT: its checks of the FP8 / FP6 / FP4 and bf16 converters for every probed notebook;
-# GPU_PROBE_LDS: its checks of the LDS, the transposing LDS reads and the lane exchanges for every probed notebook
+# GPU_PROBE_LDS: its checks of the LDS, the transposing LDS reads and the lane exchanges for every probed notebook;
+# GPU_PROBE_MFMA16: its GEMM checks on the 16×16 matrix-core instruction shapes for every probed notebook
 
 
 def params_env(version: str) -> str:

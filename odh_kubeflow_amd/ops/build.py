@@ -45,7 +45,7 @@ def targets() -> Dict[str, dict]:
             "deps": [os.path.join(CSRC, "gpu_probe.h"), os.path.join(CSRC, "gpu_probe_mx.h"),
                      os.path.join(CSRC, "gpu_probe_dense.h"), os.path.join(CSRC, "gpu_probe_fp.h"),
                      os.path.join(CSRC, "gpu_probe_sparse.h"), os.path.join(CSRC, "gpu_probe_cvt.h"),
-                     os.path.join(CSRC, "gpu_probe_lds.h")],
+                     os.path.join(CSRC, "gpu_probe_lds.h"), os.path.join(CSRC, "gpu_probe_m16.h")],
             "cmd": lambda src, out: [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
                                      *src, "-o", out],
         },

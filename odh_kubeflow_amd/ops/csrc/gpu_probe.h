@@ -77,6 +77,12 @@ enum {
   ODH_TC_B8 = 1,   // one byte per element (fp8, bf8, E8M0 scales)
   ODH_TC_B4 = 2,   // two nibbles per byte, even index low (fp4)
   ODH_TC_B6 = 3,   // element k in bits [6k, 6k + 6) of a row (fp6, bf6)
+  // operand formats of the 16×16 matrix-core kernels (gpu_probe_m16.h)
+  ODH_M16_BF16 = 0,  // bfloat16, 16x16x32, fp32 accumulation
+  ODH_M16_F16 = 1,   // IEEE half, 16x16x32, fp32 accumulation
+  ODH_M16_I8 = 2,    // int8, 16x16x64, int32 accumulation
+  ODH_M16_FP8 = 3,   // OCP e4m3fn on both operands, block scaled, 16x16x128, fp32 accumulation
+  ODH_M16_FP4 = 4,   // e2m1 on both operands, block scaled, 16x16x128, fp32 accumulation
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -189,6 +195,20 @@ int odh_lds_tr_read(int check, const void* image, unsigned bytes, const uint32_t
                     hipStream_t stream);
 int odh_lds_xlane(int op, int arg, const uint32_t* in, uint32_t* out, hipStream_t stream);
 int odh_transpose_codes(int fmt, const void* src, void* dst, long R, long C, hipStream_t stream);
+// The 16×16 matrix-core shapes (fmt: ODH_M16_*; gpu_probe_m16.h): operands in the public layouts of odh_gemm_bf16
+// (bf16), odh_dense_gemm (f16, i8) and odh_mx_gemm (fp8, fp4, scales [rows][K/32]); C [M][N] fp32, int32 for i8; M
+// and N multiples of 256, K of 32 (bf16, f16), 64 (i8) or 128 (fp8, fp4).  sA, sBt and table are NULL for bf16, f16
+// and i8 (a non-NULL one is refused) and odh_mx_fill's for fp8 and fp4; the operands of the fused check are
+// odh_probe_fill's, odh_dense_fill's or odh_mx_fill's; counters as for the dense kernels.  odh_m16_one: one wave, one
+// instruction on a zero accumulator; a and b 64 lanes × 8 dwords (a format uses the low 4 or 8 of a lane), 16-byte
+// aligned; sa and sb 64 scale dwords (NULL for bf16, f16 and i8); opsel_a and opsel_b 0 … 3; d 64 × 4 dwords
+int odh_m16_gemm(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt, void* C, int M, int N, int K,
+                 hipStream_t stream);
+int odh_m16_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt,
+                              const float* table, int M, int N, int K, int* tile_xcd, int* counters,
+                              hipStream_t stream);
+int odh_m16_one(int fmt, const uint32_t* a, const uint32_t* b, const uint32_t* sa, const uint32_t* sb, int opsel_a,
+                int opsel_b, void* d, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device;
 // *out: the handle, NULL after every failure
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,

@@ -54,6 +54,10 @@
 //    odh_lds_fault_count, the host's view of what they compare; odh_lds_tr_read and odh_lds_xlane, one
 //    instruction at a time, which the lane maps were measured with; and odh_transpose_codes, packed codes [R][C]
 //    to [C][R] through those reads.
+//  * odh_m16_gemm / odh_m16_probe_gemm_verify — the same exact checks on the 16×16 shapes of the matrix-core
+//    instructions (v_mfma_f32_16x16x32_bf16 / _f16, v_mfma_i32_16x16x64_i8, v_mfma_scale_f32_16x16x128_f8f6f4 with FP8
+//    or FP4 operands; gpu_probe_m16.h), whose operand, scale and C/D maps are not the 32×32 ones, on the operands and
+//    tables of the fills above; and odh_m16_one, one instruction at a time, which the maps were measured with.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -848,6 +852,7 @@ int grid_for(size_t n, int per_block) {
 
 #include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
 #include "gpu_probe_lds.h"  // the LDS, its transposing reads, the lane exchanges and the transposer of packed codes
+#include "gpu_probe_m16.h"  // the 16×16 matrix-core shapes (bf16, f16, i8, FP8, MXFP4), on the tile helpers, ring and tables above
 
 }  // namespace
 
@@ -1431,6 +1436,50 @@ int odh_transpose_codes(int fmt, const void* src, void* dst, long R, long C, hip
     return (int)hipErrorInvalidValue;
   lds_launch_transpose(fmt, (unsigned)((R / LDS_TC_TILE) * (C / LDS_TC_TILE)), stream, (const unsigned char*)src,
                        (unsigned char*)dst, R, C);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ 16×16 shapes (gpu_probe_m16.h)
+
+// C[M][N] = A · Btᵀ for any operands (fp8, fp4: (A ∘ sA) · (Bt ∘ sBt)ᵀ for any codes and scales)
+int odh_m16_gemm(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt, void* C, int M, int N, int K,
+                 hipStream_t stream) {
+  if (!m16_ok(fmt, M, N, K) || !m16_aligned(fmt, A, Bt, sA, sBt) || !C || ((uintptr_t)C & 3))
+    return (int)hipErrorInvalidValue;
+  m16_launch_gemm<false>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA,
+                         (const uint8_t*)sBt, C, (const float*)nullptr, N, K, (int*)nullptr, (int*)nullptr,
+                         (unsigned*)nullptr, (unsigned*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// the same tiles on the operands of odh_probe_fill (bf16), odh_dense_fill (f16, i8) or odh_mx_fill (fp8, fp4, with
+// its table) with the check fused into the epilogue; counters is a counter block of this format's own
+int odh_m16_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void* sA, const void* sBt,
+                              const float* table, int M, int N, int K, int* tile_xcd, int* counters,
+                              hipStream_t stream) {
+  if (!m16_ok(fmt, M, N, K) || !m16_aligned(fmt, A, Bt, sA, sBt) || (table != nullptr) != m16_scaled(fmt) || !counters)
+    return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  m16_launch_gemm<true>(fmt, gemm256_tiles(M, N), stream, (const uint4*)A, (const uint4*)Bt, (const uint8_t*)sA,
+                        (const uint8_t*)sBt, (void*)nullptr, table, N, K, tile_xcd, counters + ODH_SLOT_XCD_BLOCKS,
+                        c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// one wave, one instruction on a zero accumulator
+int odh_m16_one(int fmt, const uint32_t* a, const uint32_t* b, const uint32_t* sa, const uint32_t* sb, int opsel_a,
+                int opsel_b, void* d, hipStream_t stream) {
+  if (!m16_fmt_ok(fmt) || !m16_aligned(fmt, a, b, sa, sb) || !d || ((uintptr_t)d & 3) || opsel_a < 0 || opsel_a > 3 ||
+      opsel_b < 0 || opsel_b > 3)
+    return (int)hipErrorInvalidValue;
+  uint32_t* out = (uint32_t*)d;
+  switch (fmt) {
+    case ODH_M16_BF16: m16_one_kernel<ODH_M16_BF16><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
+    case ODH_M16_F16: m16_one_kernel<ODH_M16_F16><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
+    case ODH_M16_I8: m16_one_kernel<ODH_M16_I8><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
+    case ODH_M16_FP8: m16_one_kernel<ODH_M16_FP8><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
+    default: m16_one_kernel<ODH_M16_FP4><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
+  }
   return (int)hipGetLastError();
 }
 

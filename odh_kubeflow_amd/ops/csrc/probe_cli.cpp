@@ -52,6 +52,13 @@
 //      their kin), one workgroup per CU and one wave per SIMD, compared in registers with closed forms
 //      (odh_lds_probe_verify): no operand buffer, a 1 KiB key table (odh_lds_fill) and a counter block per check.
 //      Its verdict is one entry for the whole step: "lds":{"ok","errors","ms","bad"}.
+//  11. with --mfma16 bf16,f16,i8,fp8,fp4 (the `amd.com/gpu-probe: "mfma16"` notebooks), after step 10, per format: the
+//      probe operands in that format's layout (odh_probe_fill, odh_dense_fill or odh_mx_fill, into the bf16 operands'
+//      buffers) and the GEMM again on the 16×16 shape of its matrix-core instruction (v_mfma_f32_16x16x32_bf16 / _f16,
+//      v_mfma_i32_16x16x64_i8, v_mfma_scale_f32_16x16x128_f8f6f4), checked in registers against the same closed form
+//      or table (odh_m16_probe_gemm_verify): the shape torch.compile's templates, Triton and CK's small tiles issue,
+//      whose operand, scale and C/D maps are not the 32×32 ones.  One entry for the whole step, as --lds:
+//      "mfma16":{"ok","errors","ms","bad"}.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -146,14 +153,15 @@ bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool lds_run(Dev& d, const Options& o, int check, Slot& s);
+bool m16_run(Dev& d, const Options& o, int fmt, Slot& s);
 int lds_blocks(int, int, int) { return ODH_LDS_BLOCKS; }
 int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
 // conversions of the fused check: four waves in each of its workgroups convert the whole family
 double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds
-enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, N_STEPS };
+// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -183,6 +191,13 @@ struct Options {
         {"xlane", ODH_LDS_XLANE}},
        // flat: six more entries would not fit the kubelet's 4096 bytes next to every other step on 8 GPUs
        lds_run, lds_blocks, nullptr, "", false, true},
+      {"mfma16", "16x16 GEMM",
+       {{"bf16", ODH_M16_BF16}, {"f16", ODH_M16_F16}, {"i8", ODH_M16_I8}, {"fp8", ODH_M16_FP8}, {"fp4", ODH_M16_FP4}},
+       // flat, as --lds: the verdict of 8 healthy GPUs with every step was 3875 bytes at its widest; the entry
+       // ,"mfma16":{"ok":true,"errors":0,"ms":99.999,"bad":""} is 53 and "mfma16":99.999, in timings_ms 16, so 3944,
+       // below 4096 - 120 = 3976.  A failing step adds "false" for "true" (1), a count of up to 10 digits (9) and a
+       // bad list of at most 19 bytes, and the verdict one error string of up to 120: 4093, which still fits
+       m16_run, nullptr, nullptr, "", false, true},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -208,7 +223,7 @@ struct Dev {
   float gemm_ms = 0, hbm_ms = 0, link_ms = 0, rccl_ms = 0;
   double malloc_ms = 0, streams_ms = 0, events_ms = 0, first_op_ms = 0;  // host-side set-up, step by step
   int link_source = -1;
-  // --mx: scales and table behind the counters
+  // --mx, and fp8 or fp4 of --mfma16: scales and table behind the counters
   void *mx_sa = nullptr, *mx_sbt = nullptr;
   float* mx_table = nullptr;
   // --sparse: metadata and table behind those
@@ -228,7 +243,8 @@ int usage(const char* argv0) {
                "[--mx fp8,fp4[,bf8,fp6,bf6]] [--dtypes f16,i8] [--fp f32,f64] [--sparse bf16,f16,i8,fp8,bf8] "
                "[--cvt fp8,bf8,fp4,fp6,bf6,bf16] [--lds mem,tr16,tr8,tr4,tr6,xlane] "
                "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
-               "[--inject-fault sparse] [--inject-fault cvt] [--inject-fault lds] [--quiet]\n",
+               "[--inject-fault sparse] [--inject-fault cvt] [--inject-fault lds] [--quiet] "
+               "[--mfma16 bf16,f16,i8,fp8,fp4] [--inject-fault mfma16]\n",
                argv0);
   return 64;
 }
@@ -299,6 +315,10 @@ bool parse(int argc, char** argv, Options& o) {
   if (!o.steps[STEP_SPARSE].asked.empty() && odh_sparse_zero_classes(o.K) != 0) return false;
   for (int fmt : o.steps[STEP_SPARSE].asked)
     if (fmt != ODH_SP_BF16 && fmt != ODH_SP_F16 && o.K % 128 != 0) return false;
+  // --mfma16: K % 64 == 0 below is a whole number of bf16, f16 and i8 instructions; fp8 and fp4 take 128 elements
+  // per instruction and check against the MX table, in which no class may expect 0
+  for (int fmt : o.steps[STEP_MFMA16].asked)
+    if ((fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4) && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
   // a step's fault needs the step
   for (const Step& s : o.steps)
     if (o.fault == s.word && s.asked.empty()) return false;
@@ -376,14 +396,17 @@ bool setup_alloc(Dev& d, const Options& o) {
   // every optional step adds a counter block per format behind the first; --mx also the scales of both
   // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
   // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
-  // --cvt adds its scale table; --lds its key table and counter blocks of its own size, with the CU bitmap
+  // --cvt adds its scale table; --lds its key table and counter blocks of its own size, with the CU bitmap;
+  // --mfma16 a counter block per format like the GEMM steps and, for fp8 or fp4, the scales and table of --mx
   size_t nslots = 0;
-  for (const Step& s : o.steps)
-    if (!s.flat) nslots += s.asked.size();
+  for (int s = 0; s < N_STEPS; ++s)
+    if (s != STEP_LDS) nslots += o.steps[s].asked.size();
   const size_t nlds_asked = o.steps[STEP_LDS].asked.size();
   const size_t lds_block = sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS);
   const size_t nldstab = nlds_asked ? align_up(ODH_LDS_TABLE) : 0, nldsc = nlds_asked ? align_up(lds_block * nlds_asked) : 0;
-  const size_t nmx = o.steps[STEP_MX].asked.size(), nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
+  size_t nmx = o.steps[STEP_MX].asked.size();  // then: whether any step needs the MX scales and table
+  for (int fmt : o.steps[STEP_MFMA16].asked) nmx += fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
+  const size_t nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
   const bool sparse = !o.steps[STEP_SPARSE].asked.empty();
@@ -606,6 +629,37 @@ bool lds_run(Dev& d, const Options& o, int check, Slot& s) {
   }
   HIP_TRY(hipEventRecord(s.e0, d.sh));
   HIP_TRY(odh_lds_probe_verify(check, d.lds_table, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a format of --mfma16, after --lds: the operands in the format's layout by the fill of that layout, into the bf16
+// operands' buffers (none is larger), then the fused check on the 16×16 instruction
+bool m16_run(Dev& d, const Options& o, int fmt, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  const bool scaled = fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
+  if (scaled)
+    HIP_TRY(odh_mx_fill(fmt == ODH_M16_FP8 ? ODH_MX_FP8 : ODH_MX_FP4, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M,
+                        o.N, o.K, d.sh));
+  else if (fmt == ODH_M16_BF16)
+    HIP_TRY(odh_probe_fill(d.a, d.bt, o.M, o.N, o.K, d.sh));
+  else
+    HIP_TRY(odh_dense_fill(fmt == ODH_M16_F16 ? ODH_DT_F16 : ODH_DT_I8, d.a, d.bt, o.M, o.N, o.K, d.sh));
+  if (o.fault == "mfma16") {
+    // A[0][0], -2 in every fill, becomes wrong, as in the steps these layouts come from: +3 as FP8 0x44 or FP4 0x05
+    // (A[0][1] is 0), +1 × ODH_DT_I8_MUL_A as int8, +1 as the half 0x3C00 or the bf16 0x3F80: row 0 of C is wrong
+    // wherever Bt[j][0] != 0
+    if (fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4 || fmt == ODH_M16_I8) {
+      HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_M16_FP8 ? 0x44 : fmt == ODH_M16_FP4 ? 0x05 : ODH_DT_I8_MUL_A, 1, d.sh));
+    } else {
+      HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_M16_F16 ? 0x00 : 0x80, 1, d.sh));
+      HIP_TRY(hipMemsetAsync((char*)d.a + 1, fmt == ODH_M16_F16 ? 0x3C : 0x3F, 1, d.sh));
+    }
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_m16_probe_gemm_verify(fmt, d.a, d.bt, scaled ? d.mx_sa : nullptr, scaled ? d.mx_sbt : nullptr,
+                                    scaled ? d.mx_table : nullptr, o.M, o.N, o.K, nullptr, s.counters, d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
@@ -873,11 +927,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, --sparse, --mx, --cvt, then --lds: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, --sparse, --mx, --cvt, --lds, then --mfma16: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -989,7 +1043,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[288] = "";  // N_STEPS entries of "word":ms,
+  char step_timing[336] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     // a flat step: total mismatches, the slowest device's kernel time summed over the checks, and the checks

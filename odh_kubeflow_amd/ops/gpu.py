@@ -150,6 +150,13 @@ LDS_XLANE_ARGS = {"bpermute": 65, "permute": 65, "swizzle": 12, "dpp": 55, "read
 # format -> (element format of the transposer, bits of an element)
 TRANSPOSE_FORMATS = {"bf16": (ODH_TC_B16, 16), "f16": (ODH_TC_B16, 16), "fp8": (ODH_TC_B8, 8), "bf8": (ODH_TC_B8, 8),
                      "fp4": (ODH_TC_B4, 4), "fp6": (ODH_TC_B6, 6), "bf6": (ODH_TC_B6, 6)}
+# operand formats of the 16×16 matrix-core kernels (csrc/gpu_probe_m16.h)
+ODH_M16_BF16 = 0  # bfloat16, 16x16x32, fp32 accumulation
+ODH_M16_F16 = 1  # IEEE half, 16x16x32, fp32 accumulation
+ODH_M16_I8 = 2  # int8, 16x16x64, int32 accumulation
+ODH_M16_FP8 = 3  # OCP e4m3fn on both operands, block scaled, 16x16x128, fp32 accumulation
+ODH_M16_FP4 = 4  # e2m1 on both operands, block scaled, 16x16x128, fp32 accumulation
+M16_FORMATS = {"bf16": ODH_M16_BF16, "f16": ODH_M16_F16, "i8": ODH_M16_I8, "fp8": ODH_M16_FP8, "fp4": ODH_M16_FP4}
 
 _vp, _i, _u32, _sz, _long = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_long
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -211,6 +218,10 @@ SIGNATURES = {
     "odh_lds_tr_read": (_i, [_i, _vp, ctypes.c_uint, _vp, _vp, _vp]),
     "odh_lds_xlane": (_i, [_i, _i, _vp, _vp, _vp]),
     "odh_transpose_codes": (_i, [_i, _vp, _vp, _long, _long, _vp]),
+    # the 16×16 matrix-core shapes (csrc/gpu_probe_m16.h)
+    "odh_m16_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "odh_m16_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "odh_m16_one": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -1199,6 +1210,172 @@ def mx_transpose(fmt, b, sb):
         sb = torch.cat([sb, torch.zeros((pad, n), dtype=torch.uint8, device=sb.device)])
     sbt = transpose_codes("fp8", sb)
     return bt, sbt[:, :k // 32].contiguous() if pad else sbt
+
+
+def _m16_format(fmt) -> int:
+    code = M16_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if code not in M16_FORMATS.values():
+        raise ValueError(f"16x16 format must be one of {sorted(M16_FORMATS)}; got {fmt!r}")
+    return code
+
+
+# by format code: elements of one instruction (= of one stage), the operands' torch dtype by name, elements
+# per operand byte or bytes per element as (numerator, denominator) of K for the row bytes, and the output dtype
+_M16_LAYOUT = {
+    ODH_M16_BF16: (32, "bfloat16", 1, 1, "float32"),
+    ODH_M16_F16: (32, "float16", 1, 1, "float32"),
+    ODH_M16_I8: (64, "int8", 1, 1, "int32"),
+    ODH_M16_FP8: (128, "uint8", 1, 1, "float32"),
+    ODH_M16_FP4: (128, "uint8", 1, 2, "float32"),
+}
+
+
+def m16_scaled(fmt) -> bool:
+    """Whether the format takes E8M0 block scales (fp8, fp4)."""
+    return _m16_format(fmt) in (ODH_M16_FP8, ODH_M16_FP4)
+
+
+def m16_stage(fmt) -> int:
+    """Elements of one instruction, which is one stage of the kernel: 32 (bf16, f16), 64 (i8), 128 (fp8, fp4)."""
+    return _M16_LAYOUT[_m16_format(fmt)][0]
+
+
+def m16_shape_ok(fmt, m: int, n: int, k: int) -> bool:
+    """256² output tiles, and K in whole instructions of the format."""
+    bk = m16_stage(fmt)
+    return m > 0 and n > 0 and k > 0 and m % 256 == 0 and n % 256 == 0 and k % bk == 0
+
+
+def _m16_operands(fmt, a, bt, sa, sbt):
+    """Checks of the 16×16 entry points, before launch: the format's dtype, one GPU, contiguous, the public layout
+    (A ``[M, row]``, Bt ``[N, row]``; fp8 and fp4 uint8 codes with uint8 scales ``[rows, K/32]``, the others no
+    scales at all).  Returns the format code, M, N, K."""
+    import torch
+
+    code = _m16_format(fmt)
+    stage, dtype, num, den, _ = _M16_LAYOUT[code]
+    want = getattr(torch, dtype)
+    name = next(k for k, v in M16_FORMATS.items() if v == code)
+    if code in (ODH_M16_FP8, ODH_M16_FP4):
+        if sa is None or sbt is None:
+            raise ValueError(f"{name} operands come with their E8M0 scales")
+        _same_gpu_2d("16x16", "operands and scales", want, f"{name} operands and scales are uint8 codes", a, bt, sa,
+                     sbt)
+    else:
+        if sa is not None or sbt is not None:
+            raise ValueError(f"{name} operands take no scales")
+        _same_gpu_2d("16x16", "operands", want, f"{name} operands are {want}", a, bt)
+    m, n, k = a.shape[0], bt.shape[0], a.shape[1] * den // num
+    if bt.shape[1] != a.shape[1] or not m16_shape_ok(code, m, n, k):
+        raise ValueError(f"M,N must be multiples of 256 and K of {stage}; got A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    if sa is not None and (tuple(sa.shape) != (m, k // 32) or tuple(sbt.shape) != (n, k // 32)):
+        raise ValueError(f"scales must be [{m},{k // 32}] and [{n},{k // 32}]; "
+                         f"got {tuple(sa.shape)} {tuple(sbt.shape)}")
+    return code, m, n, k
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def m16_gemm(fmt, a, bt, sa=None, sbt=None, out=None):
+    """``C[M,N] = A · Btᵀ`` on the 16×16 shapes of the matrix-core instructions (``v_mfma_f32_16x16x32_bf16`` /
+    ``_f16``, ``v_mfma_i32_16x16x64_i8``; fp8 and fp4: ``(A ∘ sA) · (Bt ∘ sBt)ᵀ`` on
+    ``v_mfma_scale_f32_16x16x128_f8f6f4``): fp32 out, int32 for i8."""
+    import torch
+
+    code, m, n, k = _m16_operands(fmt, a, bt, sa, sbt)
+    want = getattr(torch, _M16_LAYOUT[code][4])
+    if out is None:
+        out = torch.empty((m, n), dtype=want, device=a.device)
+    elif tuple(out.shape) != (m, n) or out.dtype != want or not out.is_contiguous() or out.device != a.device:
+        raise ValueError(f"out must be a contiguous {want} [M,N] tensor on the operands' GPU")
+    _check(load_library().odh_m16_gemm(code, a.data_ptr(), bt.data_ptr(), _ptr(sa), _ptr(sbt), out.data_ptr(), m, n, k,
+                                       _stream_ptr(a.device)))
+    return out
+
+
+def m16_verify(fmt, a, bt, sa=None, sbt=None, table=None) -> dict:
+    """The fused check of the given operands (:func:`gemm_bf16`'s probe fill, :func:`dense_fill`'s or
+    :func:`mx_fill`'s with its ``table``) on a fresh counter block; the dict of :func:`mx_verify`."""
+    import torch
+
+    code, m, n, k = _m16_operands(fmt, a, bt, sa, sbt)
+    if (table is not None) != (sa is not None):
+        raise ValueError("the table of expected values goes with the scaled formats, and only with them")
+    if table is not None and (table.dtype != torch.float32 or tuple(table.shape) != MX_TABLE
+                              or not table.is_contiguous() or table.device != a.device):
+        raise ValueError("table must be a contiguous fp32 [15,21] tensor on the operands' GPU")
+
+    def launch(tile_xcd, counters, stream):
+        return load_library().odh_m16_probe_gemm_verify(code, a.data_ptr(), bt.data_ptr(), _ptr(sa), _ptr(sbt),
+                                                        _ptr(table), m, n, k, tile_xcd, counters, stream)
+
+    return _fused_check(a.device, m, n, k, launch)
+
+
+def m16_fill(fmt, m: int, n: int, k: int, device):
+    """Fresh tensors with the probe operands of a 16×16 format, by the fill of its layout: ``(a, bt, sa, sbt,
+    table)``, the last three ``None`` for bf16, f16 and i8."""
+    import torch
+
+    code = _m16_format(fmt)
+    if not m16_shape_ok(code, m, n, k):
+        raise ValueError("16x16 probe shape must be tile aligned")
+    dev = torch.device(device)
+    _, dtype, num, den, _ = _M16_LAYOUT[code]
+    with torch.cuda.device(dev):
+        a = torch.empty((m, k * num // den), dtype=getattr(torch, dtype), device=dev)
+        bt = torch.empty((n, k * num // den), dtype=getattr(torch, dtype), device=dev)
+        if code in (ODH_M16_FP8, ODH_M16_FP4):
+            sa = torch.empty((m, k // 32), dtype=torch.uint8, device=dev)
+            sbt = torch.empty((n, k // 32), dtype=torch.uint8, device=dev)
+            table = torch.empty(MX_TABLE, dtype=torch.float32, device=dev)
+            mx_fill(ODH_MX_FP8 if code == ODH_M16_FP8 else ODH_MX_FP4, a, bt, sa, sbt, table)
+            return a, bt, sa, sbt, table
+        if code == ODH_M16_BF16:
+            if not gemm_shape_ok(m, n, k):
+                raise ValueError("bf16 probe shape must be tile aligned")
+            _check(load_library().odh_probe_fill(a.data_ptr(), bt.data_ptr(), m, n, k, _stream_ptr(dev)))
+        else:
+            dense_fill(ODH_DT_F16 if code == ODH_M16_F16 else ODH_DT_I8, a, bt)
+    return a, bt, None, None, None
+
+
+def m16_probe(device: int, fmt, m: int = PROBE_SHAPE[0], n: int = PROBE_SHAPE[1], k: int = PROBE_SHAPE[2]) -> dict:
+    """One 16×16 probe of a GPU: the fill of the format's layout, then the GEMM with the check fused into its
+    epilogue.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms`` and ``tflops`` of the check kernel."""
+    import torch
+
+    a, bt, sa, sbt, table = m16_fill(fmt, m, n, k, torch.device("cuda", device))
+    return m16_verify(fmt, a, bt, sa, sbt, table)
+
+
+def m16_one(fmt, a, b, sa=None, sb=None, opsel_a: int = 0, opsel_b: int = 0):
+    """One wave, one 16×16 instruction on a zero accumulator.  ``a`` and ``b``: int32 ``[64, 8]``, lane l's
+    registers in row l (a format uses the low 4 or 8); ``sa`` and ``sb``: int32 ``[64]`` scale VGPRs, for fp8 and
+    fp4 only.  Returns int32 ``[64, 4]``: lane l's four result registers as bits."""
+    import torch
+
+    code = _m16_format(fmt)
+    scaled = code in (ODH_M16_FP8, ODH_M16_FP4)
+    ts = [a, b] + ([sa, sb] if scaled else [])
+    if (sa is None or sb is None) if scaled else (sa is not None or sb is not None):
+        raise ValueError("scale registers go with fp8 and fp4, and only with them")
+    if any(t.dtype != torch.int32 for t in ts):
+        raise TypeError("registers are int32 bit patterns")
+    if tuple(a.shape) != (64, 8) or tuple(b.shape) != (64, 8) or (scaled and (tuple(sa.shape) != (64,)
+                                                                            or tuple(sb.shape) != (64,))):
+        raise ValueError("a and b are [64, 8], sa and sb [64]")
+    if not all(t.is_cuda and t.device == a.device and t.is_contiguous() for t in ts):
+        raise ValueError("registers must be contiguous tensors on one GPU")
+    if opsel_a not in (0, 1, 2, 3) or opsel_b not in (0, 1, 2, 3):
+        raise ValueError("opsel is 0, 1, 2 or 3")
+    with torch.cuda.device(a.device):
+        d = torch.empty((64, 4), dtype=torch.int32, device=a.device)
+        _check(load_library().odh_m16_one(code, a.data_ptr(), b.data_ptr(), _ptr(sa), _ptr(sb), opsel_a, opsel_b,
+                                          d.data_ptr(), _stream_ptr(a.device)))
+    return d
 
 
 class GpuProbe:
