@@ -13,6 +13,10 @@ holds ≥ 1 GiB of VRAM on the GPU — in a pod.  It checks, on hardware:
 * HTTPS with the agents' CA (a cleartext request gets nothing); auth: 401 without the token, 200
   with it; source health on ``/metrics``.
 
+On a kernel whose KFD has no ``proc`` directory the first check skips itself, and the agent is
+held to everything else: the pod resolves through the pod-resources API alone, to the GPU at
+torch's PCI address, and no per-pod VRAM may be reported.
+
 Reference signal replaced: Jupyter ``/api/kernels`` + ``/api/terminals`` last-activity
 (``kf/controllers/culling_controller.go:161-196,220-241``).
 """
@@ -63,8 +67,15 @@ def _torch_bdf(dev: int = 0):
     return f"{p.pci_domain_id:04x}:{p.pci_bus_id:02x}:{p.pci_device_id:02x}.0"
 
 
+KFD_PROC = "/sys/class/kfd/kfd/proc"
+# Some amdgpu kernels (a guest whose GPU is proxied from the host, for one) serve the KFD topology
+# and the busy counter but no per-process directory, and nothing else there tells one process's
+# VRAM from another's.  Where it exists every check below runs as written.
+HAS_KFD_PROC = os.path.isdir(KFD_PROC)
+
+
 def _kfd_listing() -> str:
-    root = "/sys/class/kfd/kfd/proc"
+    root = KFD_PROC
     try:
         return ", ".join(f"{p}:{sorted(os.listdir(os.path.join(root, p)))}" for p in sorted(os.listdir(root))[:8])
     except OSError as e:
@@ -125,6 +136,7 @@ def gpu_state():
     tel.close()
 
 
+@pytest.mark.skipif(not HAS_KFD_PROC, reason=f"this kernel's KFD has no per-process sysfs ({KFD_PROC})")
 def test_kfd_lists_this_process_on_torchs_gpu(gpu_state):
     mine, devs = gpu_state["mine"], gpu_state["devs"]
     assert devs, "no KFD GPU nodes under /sys"
@@ -144,14 +156,21 @@ def test_node_agent_process_on_the_mi355x(gpu_state, tmp_path, sock_dir):
     from odh_kubeflow_amd.testing.kubelet.podresources_server import FakePodResourcesServer
 
     mine, devs = gpu_state["mine"], gpu_state["devs"]
-    assert len(mine) == 1
-    dev = {d.gpu_id: d for d in devs}[mine[0].gpu_id]
+    if HAS_KFD_PROC:
+        assert len(mine) == 1
+        dev, kfd_pid = {d.gpu_id: d for d in devs}[mine[0].gpu_id], mine[0].pid
+    else:
+        # no KFD entry to find this process's GPU by: it is the one at the PCI address torch
+        # reports for cuda:0, where the load runs, and the agent must report no per-pod VRAM
+        at_torchs = [d for d in devs if d.pci_bdf.lower() == str(_torch_bdf(0)).lower()]
+        assert len(at_torchs) == 1, (devs, _torch_bdf(0))
+        dev, kfd_pid = at_torchs[0], os.getpid()
     bdf, idx = dev.pci_bdf, dev.index
 
     # this process in a pod: a host-/proc view whose cgroup file (for the host PID KFD uses)
     # names a pod UID (systemd driver) — what the DaemonSet's hostPath /proc mount shows
     uid = str(uuid.uuid4())
-    proc = tmp_path / "proc" / str(mine[0].pid)
+    proc = tmp_path / "proc" / str(kfd_pid)
     proc.mkdir(parents=True)
     (proc / "cgroup").write_text(
         f"0::/kubepods.slice/kubepods-burstable.slice/kubepods-burstable-pod{uid.replace('-', '_')}.slice/"
@@ -199,12 +218,18 @@ def test_node_agent_process_on_the_mi355x(gpu_state, tmp_path, sock_dir):
         pods = json.loads(body)
         assert pods["sources"] == {"podresources": "ok", "kfd": "ok"}, pods
         assert pods["by_name"]["team/nb-0"] == [idx]
-        assert pods["kfd_vram_bytes"][uid][str(idx)] >= 1 << 30
+        if HAS_KFD_PROC:
+            assert pods["kfd_vram_bytes"][uid][str(idx)] >= 1 << 30
+        else:
+            assert pods["kfd_vram_bytes"] == {}
         # the pod by namespace/name (pod-resources) and by UID (KFD + cgroup): the same GPU
         st, body = _get(f"{base}/gpu/activity?namespace=team&name=nb-0&pod_uid={uid}&window=2", token)
         a = json.loads(body)
         assert st == 200 and a["attributed"] and a["devices"] == [bdf], a
-        assert set(a["sources"]) == {"podresources", "kfd"} and a["pod_vram_bytes"] >= 1 << 30, a
+        if HAS_KFD_PROC:
+            assert set(a["sources"]) == {"podresources", "kfd"} and a["pod_vram_bytes"] >= 1 << 30, a
+        else:
+            assert a["sources"] == ["podresources"] and a["pod_vram_bytes"] is None, a
         # busy under an MFMA load, idle after it stops
         load = LoadGenerator(device=0, duty=1.0).start()
         time.sleep(3.0)
