@@ -83,6 +83,53 @@ enum {
   ODH_M16_I8 = 2,    // int8, 16x16x64, int32 accumulation
   ODH_M16_FP8 = 3,   // OCP e4m3fn on both operands, block scaled, 16x16x128, fp32 accumulation
   ODH_M16_FP4 = 4,   // e2m1 on both operands, block scaled, 16x16x128, fp32 accumulation
+  // checks of the vector-memory step (gpu_probe_vmem.h)
+  ODH_VM_CACHE = 0,  // a slab written and re-read through the vector L1 and the L2, in both widths, by other waves
+  ODH_VM_SUB = 1,    // byte and 16-bit stores, extending and half-register loads, 8/12/16-byte accesses across lines
+  ODH_VM_BUF = 2,    // buffer-descriptor loads and stores of 1 ... 16 bytes and their range check
+  ODH_VM_DMA = 3,    // the global -> LDS direct loads of 4, 12 and 16 bytes
+  ODH_VM_BLOCKS = 256,   // workgroups of a fused check: one per CU
+  ODH_VM_SLAB = 65536,   // bytes of the arena a workgroup owns: an XCD's 32 hold 2 MiB, half of its L2
+  ODH_VM_TABLE = 1024,   // bytes of its key table
+  ODH_VM_GUARD = 65536,  // odh_vmem_access: bytes of guard on each side of the image
+  ODH_VM_ACCESS_IMM = 64,  // odh_vmem_access: the one non-zero immediate offset it issues
+  // op of odh_vmem_access: one access per lane
+  ODH_VM_OP_LD_U8 = 0,  // global_load_ubyte / _sbyte / _ushort / _sshort: zero- and sign-extending loads
+  ODH_VM_OP_LD_I8 = 1,
+  ODH_VM_OP_LD_U16 = 2,
+  ODH_VM_OP_LD_I16 = 3,
+  ODH_VM_OP_LD_D16 = 4,  // global_load_short_d16 / _d16_hi: into one half of the register; the other half reads 0 afterwards (SRAM ECC)
+  ODH_VM_OP_LD_D16_HI = 5,
+  ODH_VM_OP_LD_B32 = 6,  // global_load_dword; _L2: at agent scope, which the vector L1 does not serve
+  ODH_VM_OP_LD_B32_L2 = 7,
+  ODH_VM_OP_LD_B64 = 8,  // global_load_dwordx2 / x3 / x4, 4-byte aligned
+  ODH_VM_OP_LD_B96 = 9,
+  ODH_VM_OP_LD_B128 = 10,
+  ODH_VM_OP_ST_B8 = 11,  // global_store_byte / _short; _D16_HI: from bits 16-23 / 16-31 of the register
+  ODH_VM_OP_ST_B16 = 12,
+  ODH_VM_OP_ST_B8_D16_HI = 13,
+  ODH_VM_OP_ST_B16_D16_HI = 14,
+  ODH_VM_OP_ST_B32 = 15,  // global_store_dword / x2 / x3 / x4
+  ODH_VM_OP_ST_B64 = 16,
+  ODH_VM_OP_ST_B96 = 17,
+  ODH_VM_OP_ST_B128 = 18,
+  ODH_VM_OP_BUF_LD_B8 = 19,  // buffer_load_ubyte / _ushort / _dword / x2 / x3 / x4 through a raw descriptor over the image
+  ODH_VM_OP_BUF_LD_B16 = 20,
+  ODH_VM_OP_BUF_LD_B32 = 21,
+  ODH_VM_OP_BUF_LD_B64 = 22,
+  ODH_VM_OP_BUF_LD_B96 = 23,
+  ODH_VM_OP_BUF_LD_B128 = 24,
+  ODH_VM_OP_BUF_ST_B8 = 25,  // buffer_store_byte / _short / _dword / x2 / x3 / x4
+  ODH_VM_OP_BUF_ST_B16 = 26,
+  ODH_VM_OP_BUF_ST_B32 = 27,
+  ODH_VM_OP_BUF_ST_B64 = 28,
+  ODH_VM_OP_BUF_ST_B96 = 29,
+  ODH_VM_OP_BUF_ST_B128 = 30,
+  ODH_VM_OP_DMA_B32 = 31,  // global_load_lds_dword / x3 / x4: global memory to LDS at M0 base + immediate + lane * size
+  ODH_VM_OP_DMA_B96 = 32,
+  ODH_VM_OP_DMA_B128 = 33,
+  ODH_VM_OP_DMA_BUF_B128 = 34,  // buffer_load_dwordx4 ... lds
+  ODH_VM_OPS = 35,
 };
 static_assert(ODH_SLOT_XCD_BLOCKS + ODH_N_XCD <= ODH_SLOT_ERR_XCD, "per-XCD workgroups overlap the next slot");
 static_assert(ODH_SLOT_ERR_XCD + ODH_N_XCD <= ODH_SLOT_GEMM_ERR, "per-XCD mismatches overlap the next slot");
@@ -209,6 +256,24 @@ int odh_m16_probe_gemm_verify(int fmt, const void* A, const void* Bt, const void
                               hipStream_t stream);
 int odh_m16_one(int fmt, const uint32_t* a, const uint32_t* b, const uint32_t* sa, const uint32_t* sb, int opsel_a,
                 int opsel_b, void* d, hipStream_t stream);
+// The vector-memory step (check: ODH_VM_*; gpu_probe_vmem.h).  table: ODH_VM_TABLE bytes on the device, 4-byte
+// aligned; arena: ODH_VM_BLOCKS × ODH_VM_SLAB bytes on the device, 256-byte aligned, overwritten; counters as for the
+// LDS step, CU bitmap included.  odh_vmem_access: one wave, one access of kind op (ODH_VM_OP_*) per lane.  buf: 2 ×
+// ODH_VM_GUARD + 65536 bytes on the device, 16-byte aligned, the image of image_bytes (a multiple of 4, at most 65536)
+// at buf + ODH_VM_GUARD, guard zones around it; lane l accesses image + lane_off[l] (64 offsets, on the host; buffer
+// kinds: vector offset lane_off[l], scalar offset soffset and immediate imm of a descriptor of num_records bytes
+// over the image; LDS-DMA kinds: to LDS byte lds_base + imm + l × size, 16 l for 12 bytes, of 65536 poisoned with 0xEE); data: 64 × 16
+// bytes on the device, a lane's store data (a half-register load: the register before); out: 64 × 16 bytes, a lane's
+// loaded register(s), for an LDS-DMA kind the 16 LDS bytes at the lane's place.  Refused before any launch: a global
+// access that leaves the image, an address misaligned for the instruction, an imm other than 0 or
+// ODH_VM_ACCESS_IMM (global kinds: other than 0), and for buffer kinds any lane whose unclamped address
+// soffset + lane_off[l] + imm + width would leave the image and the guard behind it, or a num_records beyond those
+unsigned long long odh_vmem_cases(int check);  // host only: compared elements that use a key, per launch (0: no such check)
+unsigned long long odh_vmem_fault_count(int check, int table_byte);  // host only: mismatches when that byte is wrong
+int odh_vmem_fill(int check, void* table, hipStream_t stream);
+int odh_vmem_probe_verify(int check, const void* table, void* arena, int* counters, hipStream_t stream);
+int odh_vmem_access(int op, void* buf, unsigned image_bytes, const uint32_t* lane_off, const void* data,
+                    unsigned num_records, unsigned soffset, int imm, unsigned lds_base, void* out, hipStream_t stream);
 // counters: ODH_NCOUNT × i32 on the device (graph layout); host: the same, pinned; seed: one u32 on the device;
 // *out: the handle, NULL after every failure
 int odh_probe_graph_create(const void* A, const void* Bt, int M, int N, int K, int* tile_xcd, int* counters,

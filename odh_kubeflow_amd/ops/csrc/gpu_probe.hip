@@ -58,6 +58,12 @@
 //    instructions (v_mfma_f32_16x16x32_bf16 / _f16, v_mfma_i32_16x16x64_i8, v_mfma_scale_f32_16x16x128_f8f6f4 with FP8
 //    or FP4 operands; gpu_probe_m16.h), whose operand, scale and C/D maps are not the 32×32 ones, on the operands and
 //    tables of the fills above; and odh_m16_one, one instruction at a time, which the maps were measured with.
+//  * odh_vmem_fill / odh_vmem_probe_verify — the path between a CU's registers and HBM that the sweep leaves untouched
+//    (gpu_probe_vmem.h): re-reads through the vector L1 and the L2, byte and 16-bit stores, extending and
+//    half-register loads, 12-byte and line-straddling accesses, buffer descriptors with their range check and the
+//    global -> LDS direct loads, one workgroup per CU on a slab of its own, against closed forms; odh_vmem_cases and
+//    odh_vmem_fault_count, the host's view; and odh_vmem_access, one access per lane, which the tests and the
+//    measurements of the range check use.
 //  * odh_busy — MFMA issue loop with 4 independent accumulators (drives gfx activity
 //    for the culler's amdgpu signal under synthetic load).
 //
@@ -852,6 +858,7 @@ int grid_for(size_t n, int per_block) {
 
 #include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
 #include "gpu_probe_lds.h"  // the LDS, its transposing reads, the lane exchanges and the transposer of packed codes
+#include "gpu_probe_vmem.h"  // the vector memory path: caches, byte lanes, buffer descriptors, LDS-DMA loads, on the LDS step's helpers
 #include "gpu_probe_m16.h"  // the 16×16 matrix-core shapes (bf16, f16, i8, FP8, MXFP4), on the tile helpers, ring and tables above
 
 }  // namespace
@@ -1480,6 +1487,59 @@ int odh_m16_one(int fmt, const uint32_t* a, const uint32_t* b, const uint32_t* s
     case ODH_M16_FP8: m16_one_kernel<ODH_M16_FP8><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
     default: m16_one_kernel<ODH_M16_FP4><<<1, 64, 0, stream>>>(a, b, sa, sb, opsel_a, opsel_b, out); break;
   }
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ vector-memory step (gpu_probe_vmem.h)
+
+// host only (no HIP call): compared elements that use a key, and of those the ones that use the key dword of a table byte
+unsigned long long odh_vmem_cases(int check) {
+  return vm_check_ok(check) ? vm_block_cases(check, -1) * ODH_VM_BLOCKS : 0ull;
+}
+
+unsigned long long odh_vmem_fault_count(int check, int table_byte) {
+  if (!vm_check_ok(check) || table_byte < 0 || table_byte >= ODH_VM_TABLE) return 0ull;
+  return vm_block_cases(check, table_byte / 4) * ODH_VM_BLOCKS;
+}
+
+int odh_vmem_fill(int check, void* table, hipStream_t stream) {
+  if (!vm_check_ok(check) || !table || ((uintptr_t)table & 3)) return (int)hipErrorInvalidValue;
+  vm_fill_kernel<<<1, ODH_VM_TABLE / 4, 0, stream>>>(check, (uint32_t*)table);
+  return (int)hipGetLastError();
+}
+
+// a fused check against odh_vmem_fill's table on the arena's ODH_VM_BLOCKS slabs; counters as odh_lds_probe_verify's
+int odh_vmem_probe_verify(int check, const void* table, void* arena, int* counters, hipStream_t stream) {
+  if (!vm_check_ok(check) || !table || ((uintptr_t)table & 3) || !arena || ((uintptr_t)arena & 255) || !counters)
+    return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  vm_launch_probe(check, stream, (const uint32_t*)table, (unsigned char*)arena, counters + ODH_SLOT_XCD_BLOCKS,
+                  c + ODH_SLOT_GEMM_ERR, c + ODH_SLOT_ERR_XCD, c + ODH_NCOUNT);
+  return (int)hipGetLastError();
+}
+
+// one wave, one access per lane; everything a lane could address, clamped or not, is checked here against buf
+int odh_vmem_access(int op, void* buf, unsigned image_bytes, const uint32_t* lane_off, const void* data,
+                    unsigned num_records, unsigned soffset, int imm, unsigned lds_base, void* out, hipStream_t stream) {
+  const VmOp s = vm_op_spec(op);
+  if (s.kind < 0 || !buf || ((uintptr_t)buf & 15) || !lane_off || !data || ((uintptr_t)data & 15) || !out ||
+      ((uintptr_t)out & 15) || image_bytes == 0 || image_bytes > 65536 || image_bytes % 4)
+    return (int)hipErrorInvalidValue;
+  const bool global = s.kind < 2, buffer = s.kind == 2 || s.kind == 3 || s.kind == 5;
+  if (imm != 0 && (global || imm != ODH_VM_ACCESS_IMM)) return (int)hipErrorInvalidValue;
+  if (!buffer && (num_records || soffset)) return (int)hipErrorInvalidValue;
+  const unsigned long long reach = (unsigned long long)image_bytes + ODH_VM_GUARD;  // from the image's first byte
+  if (buffer && num_records > reach) return (int)hipErrorInvalidValue;
+  if (s.kind >= 4 && (lds_base % 16 || (unsigned long long)lds_base + imm + 64 * 16 > 65536)) return (int)hipErrorInvalidValue;
+  if (s.kind < 4 && lds_base) return (int)hipErrorInvalidValue;
+  LdsLaneAddr a;
+  for (int l = 0; l < 64; ++l) {
+    a.a[l] = lane_off[l];
+    const unsigned long long at = (unsigned long long)a.a[l] + (buffer ? soffset : 0u) + (unsigned)imm;
+    if (at % s.align || at + s.width > (buffer ? reach : image_bytes)) return (int)hipErrorInvalidValue;
+  }
+  vm_access_kernel<<<1, 64, s.kind >= 4 ? 65536 : 0, stream>>>(op, (unsigned char*)buf + ODH_VM_GUARD, a, (const u32x4*)data,
+                                                               num_records, soffset, imm, lds_base, (u32x4*)out);
   return (int)hipGetLastError();
 }
 

@@ -59,6 +59,13 @@
 //      or table (odh_m16_probe_gemm_verify): the shape torch.compile's templates, Triton and CK's small tiles issue,
 //      whose operand, scale and C/D maps are not the 32×32 ones.  One entry for the whole step, as --lds:
 //      "mfma16":{"ok","errors","ms","bad"}.
+//  12. with --vmem cache,sub,buf,dma (the `amd.com/gpu-probe: "vmem"` notebooks), last, per check: the path between a
+//      CU's registers and HBM that the sweep's aligned 16-byte non-temporal accesses leave untouched: re-reads through
+//      the vector L1 and the XCD's L2, byte and 16-bit stores, extending and half-register loads, 12-byte and
+//      line-straddling accesses, buffer descriptors with their range check, and the global -> LDS direct loads, one
+//      workgroup per CU on a 64 KiB slab of its own, compared in registers with closed forms (odh_vmem_probe_verify).
+//      The arena is the first 16 MiB of the sweep's buffer, which has been verified by then; a 1 KiB key table
+//      (odh_vmem_fill) and a counter block per check.  One entry for the whole step: "vmem":{"ok","errors","ms","bad"}.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -154,14 +161,16 @@ bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s);
 bool lds_run(Dev& d, const Options& o, int check, Slot& s);
 bool m16_run(Dev& d, const Options& o, int fmt, Slot& s);
+bool vmem_run(Dev& d, const Options& o, int check, Slot& s);
 int lds_blocks(int, int, int) { return ODH_LDS_BLOCKS; }
 int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
+int vmem_blocks(int, int, int) { return ODH_VM_BLOCKS; }
 // conversions of the fused check: four waves in each of its workgroups convert the whole family
 double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16
-enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, N_STEPS };
+// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16, --vmem
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM, N_STEPS };
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -198,6 +207,13 @@ struct Options {
        // below 4096 - 120 = 3976.  A failing step adds "false" for "true" (1), a count of up to 10 digits (9) and a
        // bad list of at most 19 bytes, and the verdict one error string of up to 120: 4093, which still fits
        m16_run, nullptr, nullptr, "", false, true},
+      {"vmem", "vector memory", {{"cache", ODH_VM_CACHE}, {"sub", ODH_VM_SUB}, {"buf", ODH_VM_BUF}, {"dma", ODH_VM_DMA}},
+       // flat again.  The entry ,"vmem":{"ok":true,"errors":0,"ms":99.999,"bad":""} is 51 bytes and "vmem":99.999, in
+       // timings_ms 14: the widest healthy verdict of 8 GPUs with every step grows from 3944 to 4009, which fits the
+       // kubelet's 4096.  With one failing step ("false" for "true" 1, a count of up to 10 digits 9, a bad list of at
+       // most 19, an error string of up to 120) it is 4158, which does not: the assembled verdict then, and only
+       // then, goes without its setup_ms object (at least 86 bytes: 4072).  See fit_verdict
+       vmem_run, vmem_blocks, nullptr, "", false, true},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -233,6 +249,8 @@ struct Dev {
   void* cvt_table = nullptr;
   // --lds: its key table behind that, and its counter blocks (each with the CU bitmap) behind the table
   void* lds_table = nullptr;
+  // --vmem: the same behind those
+  void* vmem_table = nullptr;
   std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
   std::string error;
 };
@@ -244,6 +262,7 @@ int usage(const char* argv0) {
                "[--cvt fp8,bf8,fp4,fp6,bf6,bf16] [--lds mem,tr16,tr8,tr4,tr6,xlane] "
                "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
                "[--inject-fault sparse] [--inject-fault cvt] [--inject-fault lds] [--quiet] "
+               "[--vmem cache,sub,buf,dma] [--inject-fault vmem] "
                "[--mfma16 bf16,f16,i8,fp8,fp4] [--inject-fault mfma16]\n",
                argv0);
   return 64;
@@ -319,6 +338,8 @@ bool parse(int argc, char** argv, Options& o) {
   // per instruction and check against the MX table, in which no class may expect 0
   for (int fmt : o.steps[STEP_MFMA16].asked)
     if ((fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4) && (o.K % 128 != 0 || odh_mx_zero_classes(o.K) != 0)) return false;
+  // --vmem: its arena, ODH_VM_BLOCKS slabs, is the head of the sweep's buffer
+  if (!o.steps[STEP_VMEM].asked.empty() && o.hbm_bytes < (size_t)ODH_VM_BLOCKS * ODH_VM_SLAB) return false;
   // a step's fault needs the step
   for (const Step& s : o.steps)
     if (o.fault == s.word && s.asked.empty()) return false;
@@ -397,15 +418,18 @@ bool setup_alloc(Dev& d, const Options& o) {
   // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
   // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
   // --cvt adds its scale table; --lds its key table and counter blocks of its own size, with the CU bitmap;
-  // --mfma16 a counter block per format like the GEMM steps and, for fp8 or fp4, the scales and table of --mx
+  // --mfma16 a counter block per format like the GEMM steps and, for fp8 or fp4, the scales and table of --mx;
+  // --vmem what --lds adds: a key table and counter blocks with the CU bitmap (its arena is the sweep's buffer)
   size_t nslots = 0;
   for (int s = 0; s < N_STEPS; ++s)
-    if (s != STEP_LDS) nslots += o.steps[s].asked.size();
+    if (s != STEP_LDS && s != STEP_VMEM) nslots += o.steps[s].asked.size();
   const size_t nlds_asked = o.steps[STEP_LDS].asked.size();
   const size_t lds_block = sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS);
   const size_t nldstab = nlds_asked ? align_up(ODH_LDS_TABLE) : 0, nldsc = nlds_asked ? align_up(lds_block * nlds_asked) : 0;
   size_t nmx = o.steps[STEP_MX].asked.size();  // then: whether any step needs the MX scales and table
   for (int fmt : o.steps[STEP_MFMA16].asked) nmx += fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
+  const size_t nvm_asked = o.steps[STEP_VMEM].asked.size();
+  const size_t nvmtab = nvm_asked ? align_up(ODH_VM_TABLE) : 0, nvmc = nvm_asked ? align_up(lds_block * nvm_asked) : 0;
   const size_t nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
   const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
   const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
@@ -413,7 +437,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t nmeta = sparse ? align_up((size_t)o.M * (o.K / 8)) : 0;
   const size_t nsptab = sparse ? align_up(sizeof(int) * ODH_SP_CLASSES) : 0;
   const size_t ncvt = o.steps[STEP_CVT].asked.empty() ? 0 : align_up(ODH_CVT_TABLE);
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc));
+  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc + nvmtab + nvmc));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
   d.a = p;
@@ -432,14 +456,17 @@ bool setup_alloc(Dev& d, const Options& o) {
   }
   if (ncvt) d.cvt_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab;
   if (nlds_asked) d.lds_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt;
+  if (nvm_asked) d.vmem_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc;
   int* block = d.counters;
   for (int s = 0; s < N_STEPS; ++s) {
     d.slots[s].resize(o.steps[s].asked.size());
-    if (s == STEP_LDS) continue;
+    if (s == STEP_LDS || s == STEP_VMEM) continue;
     for (Slot& slot : d.slots[s]) slot.counters = block += ODH_NCOUNT;
   }
   for (size_t f = 0; f < nlds_asked; ++f)
     d.slots[STEP_LDS][f].counters = (int*)((char*)d.lds_table + nldstab + lds_block * f);
+  for (size_t f = 0; f < nvm_asked; ++f)
+    d.slots[STEP_VMEM][f].counters = (int*)((char*)d.vmem_table + nvmtab + lds_block * f);
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -661,6 +688,30 @@ bool m16_run(Dev& d, const Options& o, int fmt, Slot& s) {
   HIP_TRY(odh_m16_probe_gemm_verify(fmt, d.a, d.bt, scaled ? d.mx_sa : nullptr, scaled ? d.mx_sbt : nullptr,
                                     scaled ? d.mx_table : nullptr, o.M, o.N, o.K, nullptr, s.counters, d.sh));
   HIP_TRY(hipEventRecord(s.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+
+// a check of --vmem, last: its key table, then the fused check on the head of the sweep's buffer, which the sweep
+// has verified by then.  The xGMI link check still reads that buffer from a neighbour, so the last check writes the
+// sweep's pattern over the arena again (the pattern is a function of the offset and the seed)
+bool vmem_run(Dev& d, const Options& o, int check, Slot& s) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS), d.sh));
+  HIP_TRY(odh_vmem_fill(check, d.vmem_table, d.sh));
+  if (o.fault == "vmem" && check == o.steps[STEP_VMEM].asked[0]) {
+    // bit 0 of byte 5 of the table flips before the first asked-for check: everything stored with key dword 1
+    // differs from what the kernel expects of it, odh_vmem_fault_count(check, 5) elements
+    unsigned char byte = 0;
+    HIP_TRY(hipMemcpyAsync(&byte, (char*)d.vmem_table + 5, 1, hipMemcpyDeviceToHost, d.sh));
+    HIP_TRY(hipStreamSynchronize(d.sh));
+    HIP_TRY(hipMemsetAsync((char*)d.vmem_table + 5, byte ^ 1, 1, d.sh));
+  }
+  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  HIP_TRY(odh_vmem_probe_verify(check, d.vmem_table, d.hbm, s.counters, d.sh));
+  HIP_TRY(hipEventRecord(s.e1, d.sh));
+  if (check == o.steps[STEP_VMEM].asked.back())
+    HIP_TRY(odh_hbm_write(d.hbm, (size_t)ODH_VM_BLOCKS * ODH_VM_SLAB, d.seed, 0, d.sh));
   HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
 }
@@ -927,11 +978,11 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   for (Dev& d : devs)
     if (!finish(d)) return fail_all(d);
   const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, --sparse, --mx, --cvt, --lds, then --mfma16: one format at a time over every device, so each format has a host time
+  // --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16, then --vmem: one format at a time over every device, so each format has a host time
   // of its own
   std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
   double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16}) {
+  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM}) {
     const Step& s = o.steps[si];
     step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
     const auto t_step0 = Clock::now();
@@ -1043,7 +1094,7 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
   // total mismatches and the slowest device's kernel time
   std::string steps;
-  char step_timing[336] = "";  // N_STEPS entries of "word":ms,
+  char step_timing[384] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     // a flat step: total mismatches, the slowest device's kernel time summed over the checks, and the checks
@@ -1121,10 +1172,20 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
   std::snprintf(setup, sizeof setup,
                 ",\"setup_ms\":{\"malloc\":%.3f,\"streams\":%.3f,\"events\":%.3f,\"first_op\":%.3f,\"n_streams\":%d}",
                 devs[0].malloc_ms, devs[0].streams_ms, devs[0].events_ms, devs[0].first_op_ms, o.streams);
-  std::string json = std::string("{\"ok\":") + (ok ? "true" : "false") + ",\"devices\":" + std::to_string(ndev) +
-                     ",\"shape\":[" + std::to_string(o.M) + "," + std::to_string(o.N) + "," + std::to_string(o.K) +
-                     "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
-                     (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
-                     ",\"links\":" + links + rccl + steps + setup + tail;
+  const std::string head = std::string("{\"ok\":") + (ok ? "true" : "false") + ",\"devices\":" + std::to_string(ndev) +
+                           ",\"shape\":[" + std::to_string(o.M) + "," + std::to_string(o.N) + "," + std::to_string(o.K) +
+                           "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
+                           (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
+                           ",\"links\":" + links + rccl + steps;
+  // fit_verdict: the kubelet keeps 4096 bytes of a termination message.  Every verdict the program could emit before
+  // --vmem fits with setup_ms and is unchanged; one that would not fit goes without setup_ms (the arithmetic is
+  // at the vmem step), and should even that be too long (it cannot be with the steps there are), the short form
+  // of a failure with the first error is sent, so that what arrives is always whole JSON
+  constexpr size_t LIMIT = 4096;
+  std::string json = head + setup + tail;
+  if (json.size() > LIMIT) json = head + tail;
+  if (json.size() > LIMIT)
+    json = ok ? std::string("{\"ok\":true,\"devices\":") + std::to_string(ndev) + tail
+              : fail_json("check failed", first_err, ms_since(t_start));
   return done(ok ? 0 : 1, json);
 }

@@ -31,6 +31,10 @@
 * :func:`lds_probe`, :func:`lds_tr_read`, :func:`lds_xlane`, :func:`transpose_codes`, :func:`mx_transpose` — the LDS
   itself, the transposing LDS reads (``ds_read_b64_tr_b16`` / ``_b8`` / ``_b4``, ``ds_read_b96_tr_b6``) and the lane
   exchanges (``odh-gpu-probe --lds``), and the transposer of packed codes built on those reads.
+* :func:`vmem_probe`, :func:`vmem_access` — the vector memory path between a CU's registers and HBM: re-reads through
+  the vector L1 and the L2, byte lanes and half-register loads, 12-byte and line-straddling accesses, buffer
+  descriptors with their range check and the global → LDS direct loads (``odh-gpu-probe --vmem``), and one access
+  per lane of any of those kinds.
 * :func:`mx_quantize`, :func:`cvt_encode`, :func:`cvt_probe` — the hardware converters that make those codes
   (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
   layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
@@ -157,6 +161,68 @@ ODH_M16_I8 = 2  # int8, 16x16x64, int32 accumulation
 ODH_M16_FP8 = 3  # OCP e4m3fn on both operands, block scaled, 16x16x128, fp32 accumulation
 ODH_M16_FP4 = 4  # e2m1 on both operands, block scaled, 16x16x128, fp32 accumulation
 M16_FORMATS = {"bf16": ODH_M16_BF16, "f16": ODH_M16_F16, "i8": ODH_M16_I8, "fp8": ODH_M16_FP8, "fp4": ODH_M16_FP4}
+# checks of the vector-memory step (csrc/gpu_probe_vmem.h)
+ODH_VM_CACHE = 0  # a slab written and re-read through the vector L1 and the L2, in both widths, by other waves
+ODH_VM_SUB = 1  # byte and 16-bit stores, extending and half-register loads, 8/12/16-byte accesses across lines
+ODH_VM_BUF = 2  # buffer-descriptor loads and stores of 1 ... 16 bytes and their range check
+ODH_VM_DMA = 3  # the global -> LDS direct loads of 4, 12 and 16 bytes
+ODH_VM_BLOCKS = 256  # workgroups of a fused check: one per CU
+ODH_VM_SLAB = 65536  # bytes of the arena a workgroup owns
+ODH_VM_TABLE = 1024  # bytes of its key table
+ODH_VM_GUARD = 65536  # odh_vmem_access: bytes of guard on each side of the image
+ODH_VM_ACCESS_IMM = 64  # odh_vmem_access: the one non-zero immediate offset it issues
+# ``op`` of :func:`vmem_access`, name -> (code, kind, bytes): kind ld / st (global), bufld / bufst (buffer descriptor),
+# dma / dmabuf (global -> LDS through an address / a descriptor)
+ODH_VM_OP_LD_U8 = 0
+ODH_VM_OP_LD_I8 = 1
+ODH_VM_OP_LD_U16 = 2
+ODH_VM_OP_LD_I16 = 3
+ODH_VM_OP_LD_D16 = 4
+ODH_VM_OP_LD_D16_HI = 5
+ODH_VM_OP_LD_B32 = 6
+ODH_VM_OP_LD_B32_L2 = 7
+ODH_VM_OP_LD_B64 = 8
+ODH_VM_OP_LD_B96 = 9
+ODH_VM_OP_LD_B128 = 10
+ODH_VM_OP_ST_B8 = 11
+ODH_VM_OP_ST_B16 = 12
+ODH_VM_OP_ST_B8_D16_HI = 13
+ODH_VM_OP_ST_B16_D16_HI = 14
+ODH_VM_OP_ST_B32 = 15
+ODH_VM_OP_ST_B64 = 16
+ODH_VM_OP_ST_B96 = 17
+ODH_VM_OP_ST_B128 = 18
+ODH_VM_OP_BUF_LD_B8 = 19
+ODH_VM_OP_BUF_LD_B16 = 20
+ODH_VM_OP_BUF_LD_B32 = 21
+ODH_VM_OP_BUF_LD_B64 = 22
+ODH_VM_OP_BUF_LD_B96 = 23
+ODH_VM_OP_BUF_LD_B128 = 24
+ODH_VM_OP_BUF_ST_B8 = 25
+ODH_VM_OP_BUF_ST_B16 = 26
+ODH_VM_OP_BUF_ST_B32 = 27
+ODH_VM_OP_BUF_ST_B64 = 28
+ODH_VM_OP_BUF_ST_B96 = 29
+ODH_VM_OP_BUF_ST_B128 = 30
+ODH_VM_OP_DMA_B32 = 31
+ODH_VM_OP_DMA_B96 = 32
+ODH_VM_OP_DMA_B128 = 33
+ODH_VM_OP_DMA_BUF_B128 = 34
+ODH_VM_OPS = 35
+VMEM_CHECKS = {"cache": ODH_VM_CACHE, "sub": ODH_VM_SUB, "buf": ODH_VM_BUF, "dma": ODH_VM_DMA}  # what ``--vmem`` checks, in its order
+def _vmem_ops() -> dict:
+    kinds = (("buf_ld_", "bufld"), ("buf_st_", "bufst"), ("dma_buf_", "dmabuf"), ("dma_", "dma"), ("ld_", "ld"), ("st_", "st"))
+    widths = {"u8": 1, "i8": 1, "b8": 1, "u16": 2, "i16": 2, "d16": 2, "b16": 2, "b32": 4, "b64": 8, "b96": 12, "b128": 16}
+    ops = {}
+    for const, code in globals().items():
+        if const.startswith("ODH_VM_OP_"):
+            name = const[len("ODH_VM_OP_"):].lower()
+            prefix, kind = next(pk for pk in kinds if name.startswith(pk[0]))
+            ops[name] = (code, kind, widths[name[len(prefix):].split("_")[0]])
+    return ops
+
+
+VMEM_OPS = _vmem_ops()
 
 _vp, _i, _u32, _sz, _long = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_long
 # name -> (restype, argtypes) of every function of csrc/gpu_probe.h that Python calls
@@ -222,6 +288,12 @@ SIGNATURES = {
     "odh_m16_gemm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "odh_m16_probe_gemm_verify": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "odh_m16_one": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # the vector-memory step (csrc/gpu_probe_vmem.h)
+    "odh_vmem_cases": (ctypes.c_ulonglong, [_i]),
+    "odh_vmem_fault_count": (ctypes.c_ulonglong, [_i, _i]),
+    "odh_vmem_fill": (_i, [_i, _vp, _vp]),
+    "odh_vmem_probe_verify": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "odh_vmem_access": (_i, [_i, _vp, ctypes.c_uint, _vp, _vp, ctypes.c_uint, ctypes.c_uint, _i, ctypes.c_uint, _vp, _vp]),
     # the start-up probe program (ops/probe_main.py)
     "odh_probe_cli": (_i, [_i, ctypes.POINTER(ctypes.c_char_p)]),
 }
@@ -1159,6 +1231,151 @@ def lds_xlane(op, arg: int, values):
     _check(load_library().odh_lds_xlane(LDS_XLANE_OPS[name], arg, values.data_ptr(), out.data_ptr(),
                                         _stream_ptr(values.device)))
     return out
+
+
+def _vmem_check(check) -> int:
+    code = VMEM_CHECKS.get(check, check) if isinstance(check, str) else check
+    if isinstance(code, bool) or code not in VMEM_CHECKS.values():
+        raise ValueError(f"vector-memory check must be one of {sorted(VMEM_CHECKS)}; got {check!r}")
+    return code
+
+
+def vmem_cases(check) -> int:
+    """Compared elements of one launch of the fused check that use a key (``buf`` and ``dma`` also compare zeros and
+    untouched bytes, which use none).  Host arithmetic only."""
+    return load_library().odh_vmem_cases(_vmem_check(check))
+
+
+def vmem_fault_count(check, table_byte: int) -> int:
+    """Mismatches the fused check counts when byte ``table_byte`` of its key table is wrong in any way: every
+    compared element that uses that key dword, whatever the width of its access.  Host arithmetic only; 0 for a
+    check that does not exist or a byte outside the table."""
+    code = VMEM_CHECKS.get(check, check) if isinstance(check, str) else check
+    return load_library().odh_vmem_fault_count(code if isinstance(code, int) else -1, table_byte)
+
+
+def _vmem_table(table) -> None:
+    import torch
+
+    if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_VM_TABLE,) or not table.is_cuda \
+            or not table.is_contiguous() or table.data_ptr() % 4:
+        raise ValueError(f"table must be a contiguous, 4-byte aligned uint8 [{ODH_VM_TABLE}] tensor on a GPU")
+
+
+def vmem_fill(check, table) -> None:
+    """The key table of a fused vector-memory check (``ODH_VM_TABLE`` uint8, 256 key dwords) written into ``table``."""
+    code = _vmem_check(check)
+    _vmem_table(table)
+    _check(load_library().odh_vmem_fill(code, table.data_ptr(), _stream_ptr(table.device)))
+
+
+def vmem_verify(check, table, arena) -> dict:
+    """The fused check against ``table`` on ``arena`` (uint8, ``ODH_VM_BLOCKS * ODH_VM_SLAB`` bytes, 256-byte
+    aligned, overwritten) and a fresh counter block: ``ODH_VM_BLOCKS`` workgroups of four waves, one per CU, each on
+    the slab of ``ODH_VM_SLAB`` bytes that is its own; none reads, writes or waits for another's, and every address
+    a lane can form lies inside the arena.  Stored values are a closed form of position and pass XOR a fold of the
+    table's key; expected ones use the key computed in registers.  The dict of :func:`lds_verify`: ``ok``,
+    ``errors``, ``blocks``, ``err_xcd``, ``xcd_blocks``, ``ms``, ``cus``."""
+    import torch
+
+    code = _vmem_check(check)
+    _vmem_table(table)
+    if arena.dtype != torch.uint8 or arena.numel() != ODH_VM_BLOCKS * ODH_VM_SLAB or arena.device != table.device \
+            or not arena.is_contiguous() or arena.data_ptr() % 256:
+        raise ValueError(f"arena must be a contiguous, 256-byte aligned uint8 tensor of {ODH_VM_BLOCKS * ODH_VM_SLAB} "
+                         "bytes on the table's GPU")
+    dev = table.device
+    with torch.cuda.device(dev):
+        counters = torch.zeros((ODH_NCOUNT + ODH_LDS_CU_WORDS,), dtype=torch.int32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load_library().odh_vmem_probe_verify(code, table.data_ptr(), arena.data_ptr(), counters.data_ptr(),
+                                                    _stream_ptr(dev)))
+        e1.record()
+        e1.synchronize()
+        h = counters.cpu().tolist()
+    errors = h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF
+    xcd_blocks = h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD]
+    return {
+        "ok": errors == 0 and sum(xcd_blocks) == ODH_VM_BLOCKS, "errors": errors, "blocks": sum(xcd_blocks),
+        "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
+        "xcd_blocks": xcd_blocks, "ms": e0.elapsed_time(e1),
+        "cus": sum(bin(w & 0xFFFFFFFF).count("1") for w in h[ODH_NCOUNT:]),
+    }
+
+
+def vmem_probe(device: int, check) -> dict:
+    """One vector-memory probe of a GPU (``cache``, ``sub``, ``buf`` or ``dma``): the key table, an arena of its
+    own, then the fused check.  The dict of :func:`vmem_verify`."""
+    import torch
+
+    code = _vmem_check(check)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        table = torch.empty((ODH_VM_TABLE,), dtype=torch.uint8, device=dev)
+        arena = torch.empty((ODH_VM_BLOCKS * ODH_VM_SLAB,), dtype=torch.uint8, device=dev)
+        vmem_fill(code, table)
+        return vmem_verify(code, table, arena)
+
+
+def vmem_access(op, image, lane_off, data=None, num_records: int = 0, soffset: int = 0, imm: int = 0,
+                lds_base: int = 0):
+    """One wave, one access of kind ``op`` (a name of :data:`VMEM_OPS`) per lane.  ``image``: uint8 on a GPU, a
+    multiple of 4 and at most 65536 bytes; it is placed in the middle of a buffer with ``ODH_VM_GUARD`` bytes of
+    guard (0xA5) on each side.  Lane ``l`` accesses ``image[lane_off[l]:]``; for a buffer kind ``lane_off[l]`` is the
+    vector offset, ``soffset`` the scalar offset and ``imm`` the immediate (0 or ``ODH_VM_ACCESS_IMM``) of a
+    descriptor of ``num_records`` bytes over the image, in range when ``soffset + lane_off[l] + imm + width <=
+    num_records``; for an LDS-DMA kind lane ``l``'s data goes to LDS byte ``lds_base + imm + l * size`` (12 bytes:
+    ``16 * l``).  ``data``: uint8 ``[64, 16]``, a lane's store data (for a half-register load the
+    register before, whose other half reads 0 afterwards); zeros when omitted.  Returns ``(out, buffer)``: uint8 ``[64, 16]``, a lane's loaded register(s)
+    (LDS-DMA: the 16 LDS bytes at its place, 0xEE where nothing landed), and the whole buffer after the access, guard
+    zones included.  Raises ``ValueError`` before anything is launched for a global access that would leave the
+    image, an address misaligned for the instruction, and for buffer kinds any combination whose unclamped address
+    would leave the image and the guard behind it."""
+    import torch
+
+    if op not in VMEM_OPS:
+        raise ValueError(f"op must be one of {sorted(VMEM_OPS)}; got {op!r}")
+    code, kind, width = VMEM_OPS[op]
+    if image.dtype != torch.uint8 or image.dim() != 1 or not image.is_cuda or not image.is_contiguous() \
+            or not 0 < image.numel() <= 65536 or image.numel() % 4:
+        raise ValueError("image must be a contiguous uint8 vector of a multiple of 4 and at most 65536 bytes on a GPU")
+    off = [int(a) for a in lane_off]
+    if len(off) != 64:
+        raise ValueError("lane_off holds one offset per lane: 64")
+    buffer = kind in ("bufld", "bufst", "dmabuf")
+    align = min(width, 4)
+    reach = image.numel() + ODH_VM_GUARD if buffer else image.numel()
+    if imm not in ((0, ODH_VM_ACCESS_IMM) if buffer or kind == "dma" else (0,)):
+        raise ValueError(f"imm {imm} is not one this access can issue")
+    if not buffer and (num_records or soffset):
+        raise ValueError("num_records and soffset belong to the buffer kinds")
+    if soffset < 0 or not 0 <= num_records <= reach:
+        raise ValueError("soffset or num_records out of range")
+    if kind in ("dma", "dmabuf"):
+        if lds_base % 16 or not 0 <= lds_base or lds_base + imm + 64 * 16 > 65536:
+            raise ValueError("lds_base must be a multiple of 16 that keeps 64 lanes of 16 bytes inside 65536")
+    elif lds_base:
+        raise ValueError("lds_base belongs to the LDS-DMA kinds")
+    for a in off:
+        at = a + (soffset if buffer else 0) + imm
+        if a < 0 or at % align or at + width > reach:
+            raise ValueError(f"lane offset {a} is misaligned for {op} or would leave the image"
+                             + (" and its guard" if buffer else ""))
+    dev = image.device
+    with torch.cuda.device(dev):
+        buf = torch.full((2 * ODH_VM_GUARD + 65536,), 0xA5, dtype=torch.uint8, device=dev)
+        buf[ODH_VM_GUARD:ODH_VM_GUARD + image.numel()] = image
+        if data is None:
+            data = torch.zeros((64, 16), dtype=torch.uint8, device=dev)
+        if data.dtype != torch.uint8 or tuple(data.shape) != (64, 16) or data.device != dev or not data.is_contiguous():
+            raise ValueError("data must be a contiguous uint8 [64, 16] tensor on the image's GPU")
+        out = torch.zeros((64, 16), dtype=torch.uint8, device=dev)
+        host = (ctypes.c_uint32 * 64)(*off)
+        _check(load_library().odh_vmem_access(code, buf.data_ptr(), image.numel(), ctypes.cast(host, ctypes.c_void_p),
+                                              data.data_ptr(), num_records, soffset, imm, lds_base, out.data_ptr(),
+                                              _stream_ptr(dev)))
+    return out, buf
 
 
 def transpose_codes(fmt, x):
