@@ -93,6 +93,7 @@
 #include <string>
 #include <thread>
 #include <unistd.h>
+#include <utility>
 #include <vector>
 
 #include "gpu_probe.h"
@@ -116,6 +117,11 @@ struct Slot {
   float ms = 0;
 };
 
+// What differs between the optional steps, for one format on one device, on the sweep's stream (step_run does the
+// rest): the fill and, if fault, the corruption; then the one fused verify launch
+using Prepare = bool(Dev&, const Options&, int fmt, bool fault);
+using Check = bool(Dev&, const Options&, int fmt, int* counters);
+
 // An optional step (--mx, --dtypes, --fp, --sparse: per asked-for format, the probe operands re-encoded into
 // the bf16 operands' buffers and a fused check of that format's matrix-core instruction; --cvt: per format, the
 // fused check of its converter).
@@ -123,14 +129,14 @@ struct Step {
   const char* word;  // the option (--word), the --inject-fault word and the verdict key
   const char* what;  // in the error string: "<N> <what> mismatches"
   std::vector<std::pair<const char*, int>> formats;  // name <-> code
-  // one format on one device, on the sweep's stream: fill, the fault if asked for, event, fused
-  // verify, event, the counters copied back
-  bool (*run)(Dev&, const Options&, int fmt, Slot&);
+  Prepare* prepare;
+  Check* check;
   int (*tiles)(int fmt, int M, int N) = nullptr;  // workgroups of a format's kernel; null: the bf16 GEMM's
   double (*work)(int fmt) = nullptr;  // operations of a format's kernel; null: the GEMM's 2 M N K, reported as tflops
   const char* rate = "tflops";        // the verdict key of the rate: with work, operations per nanosecond
   bool host_ms = true;                // whether a format's entry ends with its host time
   bool flat = false;                  // one entry for the whole step instead of one per format (--lds)
+  int block = ODH_NCOUNT;             // ints of a format's counter block (--lds, --vmem: with the CU bitmap behind it)
   std::vector<int> asked = {};  // the formats to check, in the order given
 
   const char* name(int fmt) const {
@@ -154,23 +160,18 @@ struct Step {
   }
 };
 
-bool mx_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool dt_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool fp_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool sp_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool lds_run(Dev& d, const Options& o, int check, Slot& s);
-bool m16_run(Dev& d, const Options& o, int fmt, Slot& s);
-bool vmem_run(Dev& d, const Options& o, int check, Slot& s);
+Prepare mx_prepare, dt_prepare, fp_prepare, sp_prepare, cvt_prepare, lds_prepare, m16_prepare, vmem_prepare;
+Check mx_check, dt_check, fp_check, sp_check, cvt_check, lds_check, m16_check, vmem_check;
 int lds_blocks(int, int, int) { return ODH_LDS_BLOCKS; }
 int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
 int vmem_blocks(int, int, int) { return ODH_VM_BLOCKS; }
 // conversions of the fused check: four waves in each of its workgroups convert the whole family
 double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
-// the steps in the verdict's order, which is also the order of their counter blocks and events;
-// they run --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16, --vmem
+// the steps in the verdict's order, which is also the order of their counter blocks and events
 enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM, N_STEPS };
+// the order they run in
+constexpr int RUN_ORDER[N_STEPS] = {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM};
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -183,37 +184,37 @@ struct Options {
   Step steps[N_STEPS] = {
       {"mx", "MX GEMM",
        {{"fp8", ODH_MX_FP8}, {"fp4", ODH_MX_FP4}, {"bf8", ODH_MX_BF8}, {"fp6", ODH_MX_FP6}, {"bf6", ODH_MX_BF6}},
-       mx_run},
-      {"dtypes", "GEMM", {{"f16", ODH_DT_F16}, {"i8", ODH_DT_I8}}, dt_run},  // tflops counts integer operations for i8
-      {"fp", "GEMM", {{"f32", ODH_FP_F32}, {"f64", ODH_FP_F64}}, fp_run, odh_fp_tiles},
+       mx_prepare, mx_check},
+      {"dtypes", "GEMM", {{"f16", ODH_DT_F16}, {"i8", ODH_DT_I8}}, dt_prepare, dt_check},  // tflops counts integer operations for i8
+      {"fp", "GEMM", {{"f32", ODH_FP_F32}, {"f64", ODH_FP_F64}}, fp_prepare, fp_check, odh_fp_tiles},
       {"sparse", "sparse GEMM",  // tflops counts the dense-equivalent 2 M N K
        {{"bf16", ODH_SP_BF16}, {"f16", ODH_SP_F16}, {"i8", ODH_SP_I8}, {"fp8", ODH_SP_FP8}, {"bf8", ODH_SP_BF8}},
-       sp_run},
+       sp_prepare, sp_check},
       {"cvt", "conversion",  // gcvt_s: family cases per nanosecond over all waves
        {{"fp8", ODH_CVT_FP8}, {"bf8", ODH_CVT_BF8}, {"fp4", ODH_CVT_FP4}, {"fp6", ODH_CVT_FP6}, {"bf6", ODH_CVT_BF6},
         {"bf16", ODH_CVT_BF16}},
        // no host_ms: with it the verdict of 8 healthy GPUs and every step is 3914 bytes at the widest, which one
        // failing check's error string takes to the kubelet's 4096; its entries are 17 bytes shorter each
-       cvt_run, cvt_blocks, cvt_work, "gcvt_s", false},
+       cvt_prepare, cvt_check, cvt_blocks, cvt_work, "gcvt_s", false},
       {"lds", "LDS",
        {{"mem", ODH_LDS_MEM}, {"tr16", ODH_LDS_TR16}, {"tr8", ODH_LDS_TR8}, {"tr4", ODH_LDS_TR4}, {"tr6", ODH_LDS_TR6},
         {"xlane", ODH_LDS_XLANE}},
        // flat: six more entries would not fit the kubelet's 4096 bytes next to every other step on 8 GPUs
-       lds_run, lds_blocks, nullptr, "", false, true},
+       lds_prepare, lds_check, lds_blocks, nullptr, "", false, true, ODH_NCOUNT + ODH_LDS_CU_WORDS},
       {"mfma16", "16x16 GEMM",
        {{"bf16", ODH_M16_BF16}, {"f16", ODH_M16_F16}, {"i8", ODH_M16_I8}, {"fp8", ODH_M16_FP8}, {"fp4", ODH_M16_FP4}},
        // flat, as --lds: the verdict of 8 healthy GPUs with every step was 3875 bytes at its widest; the entry
        // ,"mfma16":{"ok":true,"errors":0,"ms":99.999,"bad":""} is 53 and "mfma16":99.999, in timings_ms 16, so 3944,
        // below 4096 - 120 = 3976.  A failing step adds "false" for "true" (1), a count of up to 10 digits (9) and a
        // bad list of at most 19 bytes, and the verdict one error string of up to 120: 4093, which still fits
-       m16_run, nullptr, nullptr, "", false, true},
+       m16_prepare, m16_check, nullptr, nullptr, "", false, true},
       {"vmem", "vector memory", {{"cache", ODH_VM_CACHE}, {"sub", ODH_VM_SUB}, {"buf", ODH_VM_BUF}, {"dma", ODH_VM_DMA}},
        // flat again.  The entry ,"vmem":{"ok":true,"errors":0,"ms":99.999,"bad":""} is 51 bytes and "vmem":99.999, in
        // timings_ms 14: the widest healthy verdict of 8 GPUs with every step grows from 3944 to 4009, which fits the
        // kubelet's 4096.  With one failing step ("false" for "true" 1, a count of up to 10 digits 9, a bad list of at
        // most 19, an error string of up to 120) it is 4158, which does not: the assembled verdict then, and only
        // then, goes without its setup_ms object (at least 86 bytes: 4072).  See fit_verdict
-       vmem_run, vmem_blocks, nullptr, "", false, true},
+       vmem_prepare, vmem_check, vmem_blocks, nullptr, "", false, true, ODH_NCOUNT + ODH_LDS_CU_WORDS},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -247,11 +248,12 @@ struct Dev {
   int* sp_table = nullptr;
   // --cvt: the scale table behind those
   void* cvt_table = nullptr;
-  // --lds: its key table behind that, and its counter blocks (each with the CU bitmap) behind the table
+  // --lds: its key table behind that
   void* lds_table = nullptr;
-  // --vmem: the same behind those
+  // --vmem: the same behind that
   void* vmem_table = nullptr;
-  std::vector<Slot> slots[N_STEPS];  // per step, one per asked-for format: counter blocks behind the first
+  // per step, one per asked-for format: counter blocks behind the first, in the counters region
+  std::vector<Slot> slots[N_STEPS];
   std::string error;
 };
 
@@ -410,63 +412,57 @@ size_t align_up(size_t x) { return (x + 4095) & ~(size_t)4095; }
 // then the streams and events.  Host-side set-up time is what the notebook pod waits for.
 bool setup_alloc(Dev& d, const Options& o) {
   HIP_TRY(hipSetDevice(d.index));
-  const size_t esz = operand_esize(o);
-  const size_t na = align_up((size_t)o.M * o.K * esz), nb = align_up((size_t)o.N * o.K * esz);
-  const size_t nh = align_up(o.hbm_bytes), nt = align_up(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
   auto t0 = Clock::now();
-  // every optional step adds a counter block per format behind the first; --mx also the scales of both
-  // operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
+  // the carve: every region starts at the offset the one before it ended at, rounded up to 4 KiB
+  size_t total = 0;
+  auto take = [&total](size_t bytes) { return std::exchange(total, total + align_up(bytes)); };
+  // every optional step adds a counter block per format behind the first, of its own size; --mx also the scales of
+  // both operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
   // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
-  // --cvt adds its scale table; --lds its key table and counter blocks of its own size, with the CU bitmap;
-  // --mfma16 a counter block per format like the GEMM steps and, for fp8 or fp4, the scales and table of --mx;
-  // --vmem what --lds adds: a key table and counter blocks with the CU bitmap (its arena is the sweep's buffer)
-  size_t nslots = 0;
-  for (int s = 0; s < N_STEPS; ++s)
-    if (s != STEP_LDS && s != STEP_VMEM) nslots += o.steps[s].asked.size();
-  const size_t nlds_asked = o.steps[STEP_LDS].asked.size();
-  const size_t lds_block = sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS);
-  const size_t nldstab = nlds_asked ? align_up(ODH_LDS_TABLE) : 0, nldsc = nlds_asked ? align_up(lds_block * nlds_asked) : 0;
-  size_t nmx = o.steps[STEP_MX].asked.size();  // then: whether any step needs the MX scales and table
-  for (int fmt : o.steps[STEP_MFMA16].asked) nmx += fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
-  const size_t nvm_asked = o.steps[STEP_VMEM].asked.size();
-  const size_t nvmtab = nvm_asked ? align_up(ODH_VM_TABLE) : 0, nvmc = nvm_asked ? align_up(lds_block * nvm_asked) : 0;
-  const size_t nc = align_up(sizeof(int) * ODH_NCOUNT * (1 + nslots));
-  const size_t nsa = nmx ? align_up((size_t)o.M * (o.K / 32)) : 0, nsb = nmx ? align_up((size_t)o.N * (o.K / 32)) : 0;
-  const size_t ntab = nmx ? align_up(sizeof(float) * ODH_MX_CLASSES) : 0;
-  const bool sparse = !o.steps[STEP_SPARSE].asked.empty();
-  const size_t nmeta = sparse ? align_up((size_t)o.M * (o.K / 8)) : 0;
-  const size_t nsptab = sparse ? align_up(sizeof(int) * ODH_SP_CLASSES) : 0;
-  const size_t ncvt = o.steps[STEP_CVT].asked.empty() ? 0 : align_up(ODH_CVT_TABLE);
-  HIP_TRY(hipMalloc(&d.block, na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc + nvmtab + nvmc));
+  // --cvt adds its scale table; --lds its key table; --mfma16, for fp8 or fp4, the scales and table of --mx;
+  // --vmem a key table as --lds (its arena is the sweep's buffer)
+  size_t ncount = ODH_NCOUNT;  // ints of the counters region
+  for (const Step& s : o.steps) ncount += s.block * s.asked.size();
+  bool mx = !o.steps[STEP_MX].asked.empty();  // whether any step needs the MX scales and table
+  for (int fmt : o.steps[STEP_MFMA16].asked) mx = mx || fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
+  const bool sparse = !o.steps[STEP_SPARSE].asked.empty(), cvt = !o.steps[STEP_CVT].asked.empty();
+  const bool lds = !o.steps[STEP_LDS].asked.empty(), vmem = !o.steps[STEP_VMEM].asked.empty();
+  const size_t esz = operand_esize(o);
+  const size_t at_a = take((size_t)o.M * o.K * esz), at_bt = take((size_t)o.N * o.K * esz), at_hbm = take(o.hbm_bytes);
+  const size_t at_tile_xcd = take(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
+  const size_t at_counters = take(sizeof(int) * ncount);
+  const size_t at_mx_sa = mx ? take((size_t)o.M * (o.K / 32)) : 0, at_mx_sbt = mx ? take((size_t)o.N * (o.K / 32)) : 0;
+  const size_t at_mx_table = mx ? take(sizeof(float) * ODH_MX_CLASSES) : 0;
+  const size_t at_sp_meta = sparse ? take((size_t)o.M * (o.K / 8)) : 0;
+  const size_t at_sp_table = sparse ? take(sizeof(int) * ODH_SP_CLASSES) : 0;
+  const size_t at_cvt_table = cvt ? take(ODH_CVT_TABLE) : 0;
+  const size_t at_lds_table = lds ? take(ODH_LDS_TABLE) : 0;
+  const size_t at_vmem_table = vmem ? take(ODH_VM_TABLE) : 0;
+  HIP_TRY(hipMalloc(&d.block, total));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
-  d.a = p;
-  d.bt = p + na;
-  d.hbm = p + na + nb;
-  d.tile_xcd = (int*)(p + na + nb + nh);
-  d.counters = (int*)(p + na + nb + nh + nt);
-  if (nmx) {
-    d.mx_sa = p + na + nb + nh + nt + nc;
-    d.mx_sbt = p + na + nb + nh + nt + nc + nsa;
-    d.mx_table = (float*)(p + na + nb + nh + nt + nc + nsa + nsb);
+  d.a = p + at_a;
+  d.bt = p + at_bt;
+  d.hbm = p + at_hbm;
+  d.tile_xcd = (int*)(p + at_tile_xcd);
+  d.counters = (int*)(p + at_counters);
+  if (mx) {
+    d.mx_sa = p + at_mx_sa;
+    d.mx_sbt = p + at_mx_sbt;
+    d.mx_table = (float*)(p + at_mx_table);
   }
   if (sparse) {
-    d.sp_meta = p + na + nb + nh + nt + nc + nsa + nsb + ntab;
-    d.sp_table = (int*)(p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta);
+    d.sp_meta = p + at_sp_meta;
+    d.sp_table = (int*)(p + at_sp_table);
   }
-  if (ncvt) d.cvt_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab;
-  if (nlds_asked) d.lds_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt;
-  if (nvm_asked) d.vmem_table = p + na + nb + nh + nt + nc + nsa + nsb + ntab + nmeta + nsptab + ncvt + nldstab + nldsc;
-  int* block = d.counters;
+  if (cvt) d.cvt_table = p + at_cvt_table;
+  if (lds) d.lds_table = p + at_lds_table;
+  if (vmem) d.vmem_table = p + at_vmem_table;
+  int* block = d.counters + ODH_NCOUNT;
   for (int s = 0; s < N_STEPS; ++s) {
     d.slots[s].resize(o.steps[s].asked.size());
-    if (s == STEP_LDS || s == STEP_VMEM) continue;
-    for (Slot& slot : d.slots[s]) slot.counters = block += ODH_NCOUNT;
+    for (Slot& slot : d.slots[s]) slot.counters = std::exchange(block, block + o.steps[s].block);
   }
-  for (size_t f = 0; f < nlds_asked; ++f)
-    d.slots[STEP_LDS][f].counters = (int*)((char*)d.lds_table + nldstab + lds_block * f);
-  for (size_t f = 0; f < nvm_asked; ++f)
-    d.slots[STEP_VMEM][f].counters = (int*)((char*)d.vmem_table + nvmtab + lds_block * f);
   t0 = Clock::now();
   if (o.streams >= 1) HIP_TRY(hipStreamCreateWithFlags(&d.sg, hipStreamNonBlocking));
   if (o.streams == 2) HIP_TRY(hipStreamCreateWithFlags(&d.sh, hipStreamNonBlocking));
@@ -482,9 +478,10 @@ bool setup_alloc(Dev& d, const Options& o) {
     }
   d.events_ms = ms_since(t0);
   // the first operation on the stream: on the null stream it creates the hardware queue, here
-  // while the other thread is still loading the code object
+  // while the other thread is still loading the code object.  It clears every step's counter block: nothing writes
+  // one before its kernel, and finish drains this stream before the first step starts
   t0 = Clock::now();
-  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ODH_NCOUNT * (1 + nslots), d.sg));
+  HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(int) * ncount, d.sg));
   d.first_op_ms = ms_since(t0);
   return true;
 }
@@ -542,10 +539,9 @@ bool finish(Dev& d) {
 
 // a format of --mx, after the sweep: the operands re-encoded into the bf16 operands' buffers (that
 // GEMM is done, and the codes are no larger) with their scales and the table, then the fused check
-bool mx_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
+bool mx_prepare(Dev& d, const Options& o, int fmt, bool fault) {
   HIP_TRY(odh_mx_fill(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, d.sh));
-  if (o.fault == "mx") {
+  if (fault) {
     // A[0][0] becomes +3 (A[0][1] is 0, so byte 0 holds nothing else that is set in FP4's high nibble
     // or the packed formats' upper two bits): row 0 of C is wrong wherever Bt[j][0] != 0
     const int three = fmt == ODH_MX_FP4   ? 0x05
@@ -555,20 +551,19 @@ bool mx_run(Dev& d, const Options& o, int fmt, Slot& s) {
                                           : 0x44;
     HIP_TRY(hipMemsetAsync(d.a, three, 1, d.sh));
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, s.counters,
+  return true;
+}
+bool mx_check(Dev& d, const Options& o, int fmt, int* counters) {
+  HIP_TRY(odh_mx_probe_gemm_verify(fmt, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M, o.N, o.K, nullptr, counters,
                                    d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
   return true;
 }
 
 // a format of --dtypes, after the sweep and before --mx: the operands re-encoded into the bf16
 // operands' buffers (halves are as large, int8 half as large), then the fused check
-bool dt_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
+bool dt_prepare(Dev& d, const Options& o, int fmt, bool fault) {
   HIP_TRY(odh_dense_fill(fmt, d.a, d.bt, o.M, o.N, o.K, d.sh));
-  if (o.fault == "dtypes") {
+  if (fault) {
     // A[0][0] becomes +1 (the half 0x3C00, or the int8 25 = 1 × ODH_DT_I8_MUL_A): row 0 of C is
     // wrong wherever Bt[j][0] != 0
     if (fmt == ODH_DT_I8) {
@@ -578,19 +573,18 @@ bool dt_run(Dev& d, const Options& o, int fmt, Slot& s) {
       HIP_TRY(hipMemsetAsync((char*)d.a + 1, 0x3C, 1, d.sh));
     }
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+bool dt_check(Dev& d, const Options& o, int fmt, int* counters) {
+  HIP_TRY(odh_dense_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, counters, d.sh));
   return true;
 }
 
 // a format of --fp, after --dtypes and before --mx: the operands times odd constants as floats or
 // doubles into the operands' buffers (sized for the widest asked-for format), then the fused check
-bool fp_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
+bool fp_prepare(Dev& d, const Options& o, int fmt, bool fault) {
   HIP_TRY(odh_fp_fill(fmt, d.a, d.bt, o.M, o.N, o.K, d.sh));
-  if (o.fault == "fp") {
+  if (fault) {
     // A[0][0] becomes +MUL_A (the fill has -2 MUL_A): row 0 of C is wrong wherever Bt[j][0] != 0
     static const float one32 = ODH_FP_F32_MUL_A;
     static const double one64 = ODH_FP_F64_MUL_A;
@@ -599,120 +593,114 @@ bool fp_run(Dev& d, const Options& o, int fmt, Slot& s) {
     else
       HIP_TRY(hipMemcpyAsync(d.a, &one32, sizeof one32, hipMemcpyHostToDevice, d.sh));
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_fp_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+bool fp_check(Dev& d, const Options& o, int fmt, int* counters) {
+  HIP_TRY(odh_fp_probe_gemm_verify(fmt, d.a, d.bt, o.M, o.N, o.K, nullptr, counters, d.sh));
   return true;
 }
 
 // a format of --sparse, after --fp and before --mx: the pruned A compressed, its metadata and the dense Bt
 // (no larger than the bf16 operands) with the table, then the fused check
-bool sp_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
+bool sp_prepare(Dev& d, const Options& o, int fmt, bool fault) {
   HIP_TRY(odh_sparse_fill(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, d.sh));
-  if (o.fault == "sparse") {
+  if (fault) {
     // the nibble of row 0, group 0 becomes the pair (0,1) (the fill has (0,3); byte 0 is 0xEC, group 1
     // in its high nibble): the kept A[0][3] = -1 meets Bt[j][1] instead of Bt[j][3], which differ for
     // every j, so row 0 of C is wrong in every column
     HIP_TRY(hipMemsetAsync(d.sp_meta, 0xE4, 1, d.sh));
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_sparse_probe_gemm_verify(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, nullptr, s.counters,
-                                       d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+bool sp_check(Dev& d, const Options& o, int fmt, int* counters) {
+  HIP_TRY(odh_sparse_probe_gemm_verify(fmt, d.a, d.sp_meta, d.bt, d.sp_table, o.M, o.N, o.K, nullptr, counters, d.sh));
   return true;
 }
 
 // a format of --cvt, after --mx: its scale table, then the fused check of its converter
-bool cvt_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
+bool cvt_prepare(Dev& d, const Options&, int fmt, bool fault) {
   HIP_TRY(odh_cvt_fill(fmt, d.cvt_table, d.sh));
-  if (o.fault == "cvt") {
+  if (fault) {
     // entry 3 of the table becomes 0 (the fill has at least 4 there): every case of that scale is divided by
     // another power of two than the one it was multiplied by (bf16: gets another exponent than it expects)
     HIP_TRY(hipMemsetAsync((char*)d.cvt_table + 3, 0, 1, d.sh));
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_cvt_probe_verify(fmt, d.cvt_table, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return true;
+}
+bool cvt_check(Dev& d, const Options&, int fmt, int* counters) {
+  HIP_TRY(odh_cvt_probe_verify(fmt, d.cvt_table, counters, d.sh));
   return true;
 }
 
-// a check of --lds, after --cvt: its key table, then the fused check; the counter block is cleared here
-bool lds_run(Dev& d, const Options& o, int check, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
-  HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS), d.sh));
+// the fault of --lds and --vmem: bit 0 of byte 5 of the key table flips (a change a 4- or 6-bit element cannot
+// miss): everything stored with key dword 1 differs from what the kernel expects of it
+bool flip_key_bit(Dev& d, void* table) {
+  unsigned char byte = 0;
+  HIP_TRY(hipMemcpyAsync(&byte, (char*)table + 5, 1, hipMemcpyDeviceToHost, d.sh));
+  HIP_TRY(hipStreamSynchronize(d.sh));
+  HIP_TRY(hipMemsetAsync((char*)table + 5, byte ^ 1, 1, d.sh));
+  return true;
+}
+
+// a check of --lds, after --cvt: its key table, then the fused check
+bool lds_prepare(Dev& d, const Options&, int check, bool fault) {
   HIP_TRY(odh_lds_fill(check, d.lds_table, d.sh));
-  if (o.fault == "lds") {
-    // bit 0 of byte 5 of the table flips (a change a 4- or 6-bit element cannot miss): everything stored with
-    // key dword 1 differs from what the kernel expects of it
-    unsigned char byte = 0;
-    HIP_TRY(hipMemcpyAsync(&byte, (char*)d.lds_table + 5, 1, hipMemcpyDeviceToHost, d.sh));
-    HIP_TRY(hipStreamSynchronize(d.sh));
-    HIP_TRY(hipMemsetAsync((char*)d.lds_table + 5, byte ^ 1, 1, d.sh));
-  }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_lds_probe_verify(check, d.lds_table, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return !fault || flip_key_bit(d, d.lds_table);
+}
+bool lds_check(Dev& d, const Options&, int check, int* counters) {
+  HIP_TRY(odh_lds_probe_verify(check, d.lds_table, counters, d.sh));
   return true;
 }
 
 // a format of --mfma16, after --lds: the operands in the format's layout by the fill of that layout, into the bf16
-// operands' buffers (none is larger), then the fused check on the 16×16 instruction
-bool m16_run(Dev& d, const Options& o, int fmt, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
-  const bool scaled = fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
-  if (scaled)
-    HIP_TRY(odh_mx_fill(fmt == ODH_M16_FP8 ? ODH_MX_FP8 : ODH_MX_FP4, d.a, d.bt, d.mx_sa, d.mx_sbt, d.mx_table, o.M,
-                        o.N, o.K, d.sh));
-  else if (fmt == ODH_M16_BF16)
-    HIP_TRY(odh_probe_fill(d.a, d.bt, o.M, o.N, o.K, d.sh));
-  else
-    HIP_TRY(odh_dense_fill(fmt == ODH_M16_F16 ? ODH_DT_F16 : ODH_DT_I8, d.a, d.bt, o.M, o.N, o.K, d.sh));
-  if (o.fault == "mfma16") {
-    // A[0][0], -2 in every fill, becomes wrong, as in the steps these layouts come from: +3 as FP8 0x44 or FP4 0x05
-    // (A[0][1] is 0), +1 × ODH_DT_I8_MUL_A as int8, +1 as the half 0x3C00 or the bf16 0x3F80: row 0 of C is wrong
-    // wherever Bt[j][0] != 0
-    if (fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4 || fmt == ODH_M16_I8) {
-      HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_M16_FP8 ? 0x44 : fmt == ODH_M16_FP4 ? 0x05 : ODH_DT_I8_MUL_A, 1, d.sh));
-    } else {
-      HIP_TRY(hipMemsetAsync(d.a, fmt == ODH_M16_F16 ? 0x00 : 0x80, 1, d.sh));
-      HIP_TRY(hipMemsetAsync((char*)d.a + 1, fmt == ODH_M16_F16 ? 0x3C : 0x3F, 1, d.sh));
-    }
+// operands' buffers (none is larger), then the fused check on the 16×16 instruction.  A[0][0], -2 in every fill,
+// becomes wrong as in the step the layout comes from
+bool m16_prepare(Dev& d, const Options& o, int fmt, bool fault) {
+  if (fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4)
+    return mx_prepare(d, o, fmt == ODH_M16_FP8 ? ODH_MX_FP8 : ODH_MX_FP4, fault);
+  if (fmt != ODH_M16_BF16) return dt_prepare(d, o, fmt == ODH_M16_F16 ? ODH_DT_F16 : ODH_DT_I8, fault);
+  HIP_TRY(odh_probe_fill(d.a, d.bt, o.M, o.N, o.K, d.sh));
+  if (fault) {
+    // +1 as the bf16 0x3F80: row 0 of C is wrong wherever Bt[j][0] != 0
+    HIP_TRY(hipMemsetAsync(d.a, 0x80, 1, d.sh));
+    HIP_TRY(hipMemsetAsync((char*)d.a + 1, 0x3F, 1, d.sh));
   }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
+  return true;
+}
+bool m16_check(Dev& d, const Options& o, int fmt, int* counters) {
+  const bool scaled = fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
   HIP_TRY(odh_m16_probe_gemm_verify(fmt, d.a, d.bt, scaled ? d.mx_sa : nullptr, scaled ? d.mx_sbt : nullptr,
-                                    scaled ? d.mx_table : nullptr, o.M, o.N, o.K, nullptr, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+                                    scaled ? d.mx_table : nullptr, o.M, o.N, o.K, nullptr, counters, d.sh));
   return true;
 }
 
 // a check of --vmem, last: its key table, then the fused check on the head of the sweep's buffer, which the sweep
-// has verified by then.  The xGMI link check still reads that buffer from a neighbour, so the last check writes the
-// sweep's pattern over the arena again (the pattern is a function of the offset and the seed)
-bool vmem_run(Dev& d, const Options& o, int check, Slot& s) {
-  HIP_TRY(hipSetDevice(d.index));
-  HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(int) * (ODH_NCOUNT + ODH_LDS_CU_WORDS), d.sh));
+// has verified by then.  Only the first asked-for check is faulted: odh_vmem_fault_count(check, 5) elements
+bool vmem_prepare(Dev& d, const Options& o, int check, bool fault) {
   HIP_TRY(odh_vmem_fill(check, d.vmem_table, d.sh));
-  if (o.fault == "vmem" && check == o.steps[STEP_VMEM].asked[0]) {
-    // bit 0 of byte 5 of the table flips before the first asked-for check: everything stored with key dword 1
-    // differs from what the kernel expects of it, odh_vmem_fault_count(check, 5) elements
-    unsigned char byte = 0;
-    HIP_TRY(hipMemcpyAsync(&byte, (char*)d.vmem_table + 5, 1, hipMemcpyDeviceToHost, d.sh));
-    HIP_TRY(hipStreamSynchronize(d.sh));
-    HIP_TRY(hipMemsetAsync((char*)d.vmem_table + 5, byte ^ 1, 1, d.sh));
-  }
-  HIP_TRY(hipEventRecord(s.e0, d.sh));
-  HIP_TRY(odh_vmem_probe_verify(check, d.vmem_table, d.hbm, s.counters, d.sh));
-  HIP_TRY(hipEventRecord(s.e1, d.sh));
-  if (check == o.steps[STEP_VMEM].asked.back())
-    HIP_TRY(odh_hbm_write(d.hbm, (size_t)ODH_VM_BLOCKS * ODH_VM_SLAB, d.seed, 0, d.sh));
-  HIP_TRY(hipMemcpyAsync(s.host, s.counters, sizeof s.host, hipMemcpyDeviceToHost, d.sh));
+  return !fault || check != o.steps[STEP_VMEM].asked[0] || flip_key_bit(d, d.vmem_table);
+}
+bool vmem_check(Dev& d, const Options&, int check, int* counters) {
+  HIP_TRY(odh_vmem_probe_verify(check, d.vmem_table, d.hbm, counters, d.sh));
+  return true;
+}
+// The xGMI link check still reads the sweep's buffer from a neighbour, so after the step the sweep's pattern is
+// written over the arena again (the pattern is a function of the offset and the seed)
+bool vmem_restore(Dev& d) {
+  HIP_TRY(hipSetDevice(d.index));
+  HIP_TRY(odh_hbm_write(d.hbm, (size_t)ODH_VM_BLOCKS * ODH_VM_SLAB, d.seed, 0, d.sh));
+  return true;
+}
+
+// one format of any step on one device, on the sweep's stream: fill, the step's fault if asked for, event, fused
+// verify, event, the counters copied back
+bool step_run(Dev& d, const Options& o, const Step& s, int fmt, Slot& slot) {
+  HIP_TRY(hipSetDevice(d.index));
+  if (!s.prepare(d, o, fmt, o.fault == s.word)) return false;
+  HIP_TRY(hipEventRecord(slot.e0, d.sh));
+  if (!s.check(d, o, fmt, slot.counters)) return false;
+  HIP_TRY(hipEventRecord(slot.e1, d.sh));
+  HIP_TRY(hipMemcpyAsync(slot.host, slot.counters, sizeof slot.host, hipMemcpyDeviceToHost, d.sh));
   return true;
 }
 
@@ -884,140 +872,11 @@ bool rccl_allreduce(std::vector<Dev>& devs, const Options& o, RcclRun& run, std:
   return true;
 }
 
-}  // namespace
-
-// ms from the spawner's CLOCK_REALTIME stamp (ODH_PROBE_T0_NS, ns) to now: process start,
-// dynamic linking of the HIP runtime; -1 when the spawner did not stamp
-double exec_ms() {
-  const char* t0 = std::getenv("ODH_PROBE_T0_NS");
-  if (!t0 || !*t0) return -1.0;
-  timespec ts;
-  clock_gettime(CLOCK_REALTIME, &ts);
-  return (ts.tv_sec * 1e9 + ts.tv_nsec - std::strtod(t0, nullptr)) / 1e6;
-}
-
-extern "C" int odh_probe_cli(int argc, char** argv) {
-  const double t_exec = exec_ms();
-  const auto t_start = Clock::now();
-  Options o;
-  if (!parse(argc, argv, o)) return usage(argc > 0 ? argv[0] : "odh-gpu-probe");
-
-  // watchdog: a wedged GPU must not hold the pod in Init forever; each call has its own flag,
-  // so a later call in the same process is never cut short by an earlier call's watchdog
-  auto finished = std::make_shared<std::atomic<bool>>(false);
-  std::thread([o, t_start, finished] {
-    const auto deadline = t_start + std::chrono::milliseconds(o.timeout_ms);
-    while (!finished->load() && Clock::now() < deadline) std::this_thread::sleep_for(std::chrono::milliseconds(5));
-    if (!finished->exchange(true)) {
-      emit(o, fail_json("timeout", "probe did not finish within " + std::to_string(o.timeout_ms) + " ms",
-                        ms_since(t_start)));
-      std::_Exit(3);
-    }
-  }).detach();
-  auto done = [&](int rc, const std::string& json) {
-    if (finished->exchange(true)) {  // the watchdog reported already and is exiting
-      for (;;) std::this_thread::sleep_for(std::chrono::seconds(1));
-    }
-    emit(o, json);
-    return rc;
-  };
-
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return done(2, fail_json("no GPU", e != hipSuccess ? hipGetErrorString(e) : "no visible device", ms_since(t_start)));
-  std::vector<Dev> devs(ndev);
-  for (int i = 0; i < ndev; ++i) devs[i].index = i;
-  e = hipSetDevice(0);
-  if (e == hipSuccess) e = hipFree(nullptr);  // context creation: the HIP-init share of the run
-  if (e != hipSuccess) return done(2, fail_json("hip init", hipGetErrorString(e), ms_since(t_start)));
-  const double t_init = ms_since(t_start);
-
-  std::string err;
-  auto fail_all = [&](Dev& d) {
-    err = "GPU " + std::to_string(d.index) + ": " + d.error;
-    for (Dev& x : devs) release(x);
-    return done(2, fail_json("hip", err, ms_since(t_start)));
-  };
-  // the code object loads on a second thread while this one allocates and makes the stream's
-  // hardware queue (both host-side work the pod waits for)
-  std::vector<int> preload_rc(ndev, 0);
-  double t_preload = 0;
-  std::thread preload([&] {
-    for (int i = 0; i < ndev; ++i) {
-      hipError_t se = hipSetDevice(i);
-      preload_rc[i] = se != hipSuccess ? (int)se : odh_probe_preload();
-    }
-    t_preload = ms_since(t_start);
-  });
-  bool alloc_ok = true;
-  Dev* bad = nullptr;
-  for (Dev& d : devs)
-    if (!setup_alloc(d, o)) {
-      alloc_ok = false;
-      bad = &d;
-      break;
-    }
-  const double t_alloc_only = ms_since(t_start);
-  preload.join();
-  if (!alloc_ok) return fail_all(*bad);
-  for (int i = 0; i < ndev; ++i)
-    if (preload_rc[i] != 0) {
-      devs[i].error = std::string("odh_probe_preload: ") + hipGetErrorString((hipError_t)preload_rc[i]);
-      return fail_all(devs[i]);
-    }
-  const double t_malloc = ms_since(t_start);
-  for (Dev& d : devs)
-    if (!setup_fill(d, o)) return fail_all(d);
-  for (Dev& d : devs)
-    if (!drain(d)) return fail_all(d);  // operands filled on every device
-  const double t_alloc = ms_since(t_start);
-  const auto t_probe0 = Clock::now();
-  for (Dev& d : devs)
-    if (!launch(d, o)) return fail_all(d);
-  for (Dev& d : devs)
-    if (!finish(d)) return fail_all(d);
-  const double probe_ms = ms_since(t_probe0);
-  // --dtypes, --fp, --sparse, --mx, --cvt, --lds, --mfma16, then --vmem: one format at a time over every device, so each format has a host time
-  // of its own
-  std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
-  double step_total_ms[N_STEPS] = {};
-  for (int si : {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM}) {
-    const Step& s = o.steps[si];
-    step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
-    const auto t_step0 = Clock::now();
-    for (size_t f = 0; f < s.asked.size(); ++f) {
-      const auto t0 = Clock::now();
-      for (Dev& d : devs)
-        if (!s.run(d, o, s.asked[f], d.slots[si][f])) return fail_all(d);
-      for (Dev& d : devs)
-        if (!step_finish(d, d.slots[si][f])) return fail_all(d);
-      step_host_ms[si][f] = ms_since(t0);
-    }
-    step_total_ms[si] = ms_since(t_step0);
-  }
-  // xGMI ring: device r reads the pattern device r-1 wrote (2 GPUs: each reads the other)
-  const auto t_link0 = Clock::now();
-  if (ndev >= 2) {
-    for (int r = 0; r < ndev; ++r)
-      if (!link_check(devs[r], devs[(r + ndev - 1) % ndev], o)) return fail_all(devs[r]);
-  }
-  for (Dev& d : devs)
-    if (!link_finish(d)) return fail_all(d);
-  const double link_ms = ndev >= 2 ? ms_since(t_link0) : 0.0;
-  RcclRun rr;
-  if (o.rccl_bytes) {
-    std::string rerr;
-    if (!rccl_allreduce(devs, o, rr, rerr)) {
-      for (Dev& x : devs) release(x);
-      return done(2, fail_json("rccl", rerr, ms_since(t_start)));
-    }
-  }
-
+// The parts of the verdict, in the order they are assembled: each clears ok if a check of its own failed, and the
+// first to fail leaves its message.  "results": per device, the bf16 GEMM and the HBM sweep
+std::string results_json(std::vector<Dev>& devs, const Options& o, bool& ok, std::string& first_err) {
   const int tiles = odh_gemm_tiles(o.M, o.N, o.K);
   const double flops = 2.0 * o.M * o.N * o.K;
-  bool ok = true;
-  std::string first_err;
   std::string res = "[";
   for (Dev& d : devs) {
     const int* h = d.host;
@@ -1050,8 +909,13 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     res += b;
   }
   res += "]";
+  return res;
+}
+
+// "links": per reader of the xGMI ring, [] on one GPU
+std::string links_json(std::vector<Dev>& devs, const Options& o, bool& ok, std::string& first_err) {
   std::string links = "[";
-  if (ndev >= 2) {
+  if (devs.size() >= 2) {
     const size_t n = (o.xgmi_bytes < o.hbm_bytes ? o.xgmi_bytes : o.hbm_bytes) & ~(size_t)15;
     for (Dev& d : devs) {
       const uint64_t lerr = u64(d.host, ODH_SLOT_CLI_XGMI_ERR);
@@ -1068,6 +932,12 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     }
   }
   links += "]";
+  return links;
+}
+
+// the "rccl" object, "" without --rccl-mib
+std::string rccl_json(std::vector<Dev>& devs, const Options& o, const RcclRun& rr, bool& ok, std::string& first_err) {
+  const int ndev = (int)devs.size();
   std::string rccl;
   if (o.rccl_bytes) {
     uint64_t rerr = 0;
@@ -1091,10 +961,16 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                   ndev > 1 ? algbw * 2.0 * (ndev - 1) / ndev : algbw);
     rccl = b;
   }
-  // the objects of the optional GEMM steps, "" without them: per format, whatever the device count,
-  // total mismatches and the slowest device's kernel time
+  return rccl;
+}
+
+// the objects of the optional steps, "" without them: per format, whatever the device count, total mismatches and
+// the slowest device's kernel time; and their entries of timings_ms into step_timing
+std::string steps_json(std::vector<Dev>& devs, const Options& o, const std::vector<double>* step_host_ms,
+                       const double* step_total_ms, char (&step_timing)[384], bool& ok, std::string& first_err) {
+  const int tiles = odh_gemm_tiles(o.M, o.N, o.K);
+  const double flops = 2.0 * o.M * o.N * o.K;
   std::string steps;
-  char step_timing[384] = "";  // N_STEPS entries of "word":ms,
   for (int si = 0; si < N_STEPS; ++si) {
     const Step& s = o.steps[si];
     // a flat step: total mismatches, the slowest device's kernel time summed over the checks, and the checks
@@ -1161,6 +1037,166 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
     const size_t at = std::strlen(step_timing);
     std::snprintf(step_timing + at, sizeof step_timing - at, "\"%s\":%.3f,", s.word, step_total_ms[si]);
   }
+  return steps;
+}
+
+// The kubelet keeps 4096 bytes of a termination message.  Every verdict the program could emit before --vmem fits
+// with setup_ms and is unchanged; one that would not fit goes without setup_ms (the arithmetic is at the vmem
+// step), and should even that be too long (it cannot be with the steps there are), the short form of a failure
+// with the first error is sent, so that what arrives is always whole JSON
+std::string fit_verdict(const std::string& head, const char* setup, const char* tail, bool ok, int ndev,
+                        const std::string& first_err, Clock::time_point t_start) {
+  constexpr size_t LIMIT = 4096;
+  std::string json = head + setup + tail;
+  if (json.size() > LIMIT) json = head + tail;
+  if (json.size() > LIMIT)
+    json = ok ? std::string("{\"ok\":true,\"devices\":") + std::to_string(ndev) + tail
+              : fail_json("check failed", first_err, ms_since(t_start));
+  return json;
+}
+
+}  // namespace
+
+// ms from the spawner's CLOCK_REALTIME stamp (ODH_PROBE_T0_NS, ns) to now: process start,
+// dynamic linking of the HIP runtime; -1 when the spawner did not stamp
+double exec_ms() {
+  const char* t0 = std::getenv("ODH_PROBE_T0_NS");
+  if (!t0 || !*t0) return -1.0;
+  timespec ts;
+  clock_gettime(CLOCK_REALTIME, &ts);
+  return (ts.tv_sec * 1e9 + ts.tv_nsec - std::strtod(t0, nullptr)) / 1e6;
+}
+
+extern "C" int odh_probe_cli(int argc, char** argv) {
+  const double t_exec = exec_ms();
+  const auto t_start = Clock::now();
+  Options o;
+  if (!parse(argc, argv, o)) return usage(argc > 0 ? argv[0] : "odh-gpu-probe");
+
+  // watchdog: a wedged GPU must not hold the pod in Init forever; each call has its own flag,
+  // so a later call in the same process is never cut short by an earlier call's watchdog
+  auto finished = std::make_shared<std::atomic<bool>>(false);
+  std::thread([o, t_start, finished] {
+    const auto deadline = t_start + std::chrono::milliseconds(o.timeout_ms);
+    while (!finished->load() && Clock::now() < deadline) std::this_thread::sleep_for(std::chrono::milliseconds(5));
+    if (!finished->exchange(true)) {
+      emit(o, fail_json("timeout", "probe did not finish within " + std::to_string(o.timeout_ms) + " ms",
+                        ms_since(t_start)));
+      std::_Exit(3);
+    }
+  }).detach();
+  auto done = [&](int rc, const std::string& json) {
+    if (finished->exchange(true)) {  // the watchdog reported already and is exiting
+      for (;;) std::this_thread::sleep_for(std::chrono::seconds(1));
+    }
+    emit(o, json);
+    return rc;
+  };
+
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0)
+    return done(2, fail_json("no GPU", e != hipSuccess ? hipGetErrorString(e) : "no visible device", ms_since(t_start)));
+  std::vector<Dev> devs(ndev);
+  for (int i = 0; i < ndev; ++i) devs[i].index = i;
+  e = hipSetDevice(0);
+  if (e == hipSuccess) e = hipFree(nullptr);  // context creation: the HIP-init share of the run
+  if (e != hipSuccess) return done(2, fail_json("hip init", hipGetErrorString(e), ms_since(t_start)));
+  const double t_init = ms_since(t_start);
+
+  std::string err;
+  auto fail_all = [&](Dev& d) {
+    err = "GPU " + std::to_string(d.index) + ": " + d.error;
+    for (Dev& x : devs) release(x);
+    return done(2, fail_json("hip", err, ms_since(t_start)));
+  };
+  // the code object loads on a second thread while this one allocates and makes the stream's
+  // hardware queue (both host-side work the pod waits for)
+  std::vector<int> preload_rc(ndev, 0);
+  double t_preload = 0;
+  std::thread preload([&] {
+    for (int i = 0; i < ndev; ++i) {
+      hipError_t se = hipSetDevice(i);
+      preload_rc[i] = se != hipSuccess ? (int)se : odh_probe_preload();
+    }
+    t_preload = ms_since(t_start);
+  });
+  Dev* bad = nullptr;
+  for (Dev& d : devs)
+    if (!setup_alloc(d, o)) {
+      bad = &d;
+      break;
+    }
+  const double t_alloc_only = ms_since(t_start);
+  preload.join();
+  if (bad) return fail_all(*bad);
+  for (int i = 0; i < ndev; ++i)
+    if (preload_rc[i] != 0) {
+      devs[i].error = std::string("odh_probe_preload: ") + hipGetErrorString((hipError_t)preload_rc[i]);
+      return fail_all(devs[i]);
+    }
+  const double t_malloc = ms_since(t_start);
+  for (Dev& d : devs)
+    if (!setup_fill(d, o)) return fail_all(d);
+  for (Dev& d : devs)
+    if (!drain(d)) return fail_all(d);  // operands filled on every device
+  const double t_alloc = ms_since(t_start);
+  const auto t_probe0 = Clock::now();
+  for (Dev& d : devs)
+    if (!launch(d, o)) return fail_all(d);
+  for (Dev& d : devs)
+    if (!finish(d)) return fail_all(d);
+  const double probe_ms = ms_since(t_probe0);
+  // the optional steps: one format at a time over every device, so each format has a host time of its own
+  std::vector<double> step_host_ms[N_STEPS];  // per asked-for format: launch on every device to the last one done
+  double step_total_ms[N_STEPS] = {};
+  for (int si : RUN_ORDER) {
+    const Step& s = o.steps[si];
+    step_host_ms[si].resize(s.asked.size());  // sized before the clock starts
+    const auto t_step0 = Clock::now();
+    for (size_t f = 0; f < s.asked.size(); ++f) {
+      const auto t0 = Clock::now();
+      for (Dev& d : devs)
+        if (!step_run(d, o, s, s.asked[f], d.slots[si][f])) return fail_all(d);
+      for (Dev& d : devs)
+        if (!step_finish(d, d.slots[si][f])) return fail_all(d);
+      step_host_ms[si][f] = ms_since(t0);
+    }
+    step_total_ms[si] = ms_since(t_step0);
+  }
+  // --vmem wrote over the head of the sweep's buffer: every device's is whole again before a neighbour reads it
+  if (!o.steps[STEP_VMEM].asked.empty()) {
+    for (Dev& d : devs)
+      if (!vmem_restore(d)) return fail_all(d);
+    for (Dev& d : devs)
+      if (!drain(d)) return fail_all(d);
+  }
+  // xGMI ring: device r reads the pattern device r-1 wrote (2 GPUs: each reads the other)
+  const auto t_link0 = Clock::now();
+  if (ndev >= 2) {
+    for (int r = 0; r < ndev; ++r)
+      if (!link_check(devs[r], devs[(r + ndev - 1) % ndev], o)) return fail_all(devs[r]);
+  }
+  for (Dev& d : devs)
+    if (!link_finish(d)) return fail_all(d);
+  const double link_ms = ndev >= 2 ? ms_since(t_link0) : 0.0;
+  RcclRun rr;
+  if (o.rccl_bytes) {
+    std::string rerr;
+    if (!rccl_allreduce(devs, o, rr, rerr)) {
+      for (Dev& x : devs) release(x);
+      return done(2, fail_json("rccl", rerr, ms_since(t_start)));
+    }
+  }
+
+  // the verdict
+  bool ok = true;
+  std::string first_err;
+  const std::string res = results_json(devs, o, ok, first_err);
+  const std::string links = links_json(devs, o, ok, first_err);
+  const std::string rccl = rccl_json(devs, o, rr, ok, first_err);
+  char step_timing[384] = "";  // N_STEPS entries of "word":ms,
+  const std::string steps = steps_json(devs, o, step_host_ms, step_total_ms, step_timing, ok, first_err);
   for (Dev& d : devs) release(d);
   char tail[640];
   std::snprintf(tail, sizeof tail,
@@ -1177,15 +1213,5 @@ extern "C" int odh_probe_cli(int argc, char** argv) {
                            "],\"hbm_mib\":" + std::to_string(o.hbm_bytes >> 20) +
                            (first_err.empty() ? "" : ",\"error\":\"" + esc(first_err) + "\"") + ",\"results\":" + res +
                            ",\"links\":" + links + rccl + steps;
-  // fit_verdict: the kubelet keeps 4096 bytes of a termination message.  Every verdict the program could emit before
-  // --vmem fits with setup_ms and is unchanged; one that would not fit goes without setup_ms (the arithmetic is
-  // at the vmem step), and should even that be too long (it cannot be with the steps there are), the short form
-  // of a failure with the first error is sent, so that what arrives is always whole JSON
-  constexpr size_t LIMIT = 4096;
-  std::string json = head + setup + tail;
-  if (json.size() > LIMIT) json = head + tail;
-  if (json.size() > LIMIT)
-    json = ok ? std::string("{\"ok\":true,\"devices\":") + std::to_string(ndev) + tail
-              : fail_json("check failed", first_err, ms_since(t_start));
-  return done(ok ? 0 : 1, json);
+  return done(ok ? 0 : 1, fit_verdict(head, setup, tail, ok, ndev, first_err, t_start));
 }

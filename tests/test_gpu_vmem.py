@@ -150,3 +150,27 @@ def test_program_runs_the_step_and_names_the_faulted_check():
     assert "vmem sub" in res["error"] and res["results"][0]["ok"] is True
     rc, res, r = _run_probe("--vmem", "cache", "--hbm-mib", "8")
     assert rc == probe_main.USAGE and r.stdout == ""
+
+
+def test_program_carves_every_region_and_any_subset():
+    """All eight steps with every format share one device block and one counters region; then regions missing
+    between present ones, with the MX tables there for ``--mfma16 fp4`` alone."""
+    every = {"mx": "fp8,fp4,bf8,fp6,bf6", "dtypes": "f16,i8", "fp": "f32,f64", "sparse": "bf16,f16,i8,fp8,bf8",
+             "cvt": "fp8,bf8,fp4,fp6,bf6,bf16", "lds": "mem,tr16,tr8,tr4,tr6,xlane", "mfma16": "bf16,f16,i8,fp8,fp4",
+             "vmem": "cache,sub,buf,dma"}
+    rc, res, r = _run_probe(*[a for word, formats in every.items() for a in ("--" + word, formats)])
+    assert rc == 0 and res["ok"], (r.stdout, r.stderr)
+    assert list(res)[-3:] == ["vmem", "setup_ms", "timings_ms"]
+    assert [k for k in res if k in every] == list(every)
+    for word, formats in every.items():
+        entries = [res[word]] if "bad" in res[word] else [res[word][f] for f in formats.split(",")]
+        assert all(e["ok"] is True and e["errors"] == 0 for e in entries), (word, res[word])
+    line = r.stdout.strip().splitlines()[-1]
+    assert len(line.encode()) < 4096
+    print("every step:", len(line), "bytes", res["timings_ms"])
+    rc, res, r = _run_probe("--sparse", "i8", "--lds", "mem", "--mfma16", "fp4", "--vmem", "buf")
+    assert rc == 0 and res["ok"], (r.stdout, r.stderr)
+    assert res["sparse"]["i8"]["ok"] is True and res["sparse"]["i8"]["errors"] == 0, res["sparse"]
+    for word in ("lds", "mfma16", "vmem"):
+        assert res[word]["ok"] is True and res[word]["errors"] == 0 and res[word]["bad"] == "", res[word]
+    assert not {"mx", "dtypes", "fp", "cvt"} & set(res)
