@@ -187,6 +187,7 @@ GPU_PROBE_CVT_FORMATS = "fp8,bf8,fp4,fp6,bf6,bf16"  # destination formats of the
 GPU_PROBE_LDS_FORMATS = "mem,tr16,tr8,tr4,tr6,xlane"  # checks of the LDS step (annotation token "lds")
 GPU_PROBE_MFMA16_FORMATS = "bf16,f16,i8,fp8,fp4"  # formats of the 16×16 matrix-core step (annotation token "mfma16")
 GPU_PROBE_VMEM_FORMATS = "cache,sub,buf,dma"  # checks of the vector-memory step (annotation token "vmem")
+GPU_PROBE_DCVT_FORMATS = "fp8,bf8,fp4,fp6,bf6"  # source formats of the decoding-converter step (annotation token "dcvt")
 
 
 GPU_PROBE_TOKENS = ("true", "rccl", "mx", "mxall", "dtypes", "false")
@@ -196,17 +197,18 @@ GPU_PROBE_CVT_TOKENS = ("cvt",)  # and since then (tests/test_probe_sparse.py ho
 GPU_PROBE_LDS_TOKENS = ("lds",)  # and since then (tests/test_probe_cvt.py holds the four above together)
 GPU_PROBE_MFMA16_TOKENS = ("mfma16",)  # and since then (tests/test_probe_lds.py holds the five above together)
 GPU_PROBE_VMEM_TOKENS = ("vmem",)  # and since then (tests/test_probe_mfma16.py holds the six above together)
+GPU_PROBE_DCVT_TOKENS = ("dcvt",)  # and since then (tests/test_probe_vmem.py holds the two above together)
 
 
 def gpu_probe_tokens(nb: dict) -> frozenset:
     """The ``amd.com/gpu-probe`` annotation as a set of tokens.  It is a comma list of ``true``,
-    ``rccl``, ``mx``, ``mxall``, ``dtypes``, ``fp``, ``sparse``, ``cvt``, ``lds``, ``mfma16``, ``vmem`` and ``false``: every one but ``true`` and ``false``
+    ``rccl``, ``mx``, ``mxall``, ``dtypes``, ``fp``, ``sparse``, ``cvt``, ``lds``, ``mfma16``, ``vmem``, ``dcvt`` and ``false``: every one but ``true`` and ``false``
     turns the probe on and adds its step, so ``"rccl,mx"`` runs both.  A value with an unknown token, or with
     ``false`` next to another token, is ignored as a whole (the empty set), like an unknown value."""
     v = (m.annotations(nb).get(GPU_PROBE_ANNOTATION) or "").strip().lower()
     tokens = frozenset(t.strip() for t in v.split(",")) if v else frozenset()
     known = GPU_PROBE_TOKENS + GPU_PROBE_MORE_TOKENS + GPU_PROBE_SPARSE_TOKENS + GPU_PROBE_CVT_TOKENS \
-        + GPU_PROBE_LDS_TOKENS + GPU_PROBE_MFMA16_TOKENS + GPU_PROBE_VMEM_TOKENS
+        + GPU_PROBE_LDS_TOKENS + GPU_PROBE_MFMA16_TOKENS + GPU_PROBE_VMEM_TOKENS + GPU_PROBE_DCVT_TOKENS
     if not tokens <= frozenset(known) or ("false" in tokens and len(tokens) > 1):
         return frozenset()
     return tokens
@@ -214,7 +216,7 @@ def gpu_probe_tokens(nb: dict) -> frozenset:
 
 def gpu_probe_enabled(nb: dict, pod_spec: dict, env: Mapping[str, str] = os.environ) -> bool:
     """The MI355X start-up probe runs for notebooks that request ``amd.com/gpu`` when the
-    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, ``"dtypes"``, ``"fp"``, ``"sparse"``, ``"cvt"``, ``"lds"``, ``"mfma16"``, ``"vmem"``, or a comma
+    Notebook says ``amd.com/gpu-probe: "true"`` (or ``"rccl"``, ``"mx"``, ``"dtypes"``, ``"fp"``, ``"sparse"``, ``"cvt"``, ``"lds"``, ``"mfma16"``, ``"vmem"``, ``"dcvt"``, or a comma
     list of them), or when the operator turned it on for every GPU notebook (``GPU_STARTUP_PROBE=true``)
     and the Notebook does not say ``"false"``.  Off by default (never on the
     reconcile path, opt-in)."""
@@ -291,10 +293,17 @@ def gpu_probe_vmem(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
     return "vmem" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_VMEM", "false") == "true"
 
 
+def gpu_probe_dcvt(nb: dict, env: Mapping[str, str] = os.environ) -> bool:
+    """Whether the probe also checks the converters that decode FP8 / FP6 / FP4 codes to float32, float16 and bfloat16
+    (``--dcvt fp8,bf8,fp4,fp6,bf6``): ``dcvt`` in ``amd.com/gpu-probe``, or ``GPU_PROBE_DCVT=true`` for every
+    probed notebook."""
+    return "dcvt" in gpu_probe_tokens(nb) or env.get("GPU_PROBE_DCVT", "false") == "true"
+
+
 def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rccl: bool = False,
                              mx: bool = False, dtypes: bool = False, mx_all: bool = False,
                              fp: bool = False, sparse: bool = False, cvt: bool = False, lds: bool = False,
-                             mfma16: bool = False, vmem: bool = False) -> dict:
+                             mfma16: bool = False, vmem: bool = False, dcvt: bool = False) -> dict:
     """Init container that proves the pod's GPUs healthy before the notebook starts.
 
     ``odh-gpu-probe`` (``ops/csrc/probe_cli.cpp``, torch-free) runs the bf16 MFMA GEMM checked
@@ -307,7 +316,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
     ``--sparse bf16,f16,i8,fp8,bf8``; ``cvt``: plus the quantising converters, ``--cvt fp8,bf8,fp4,fp6,bf6,bf16``;
     ``lds``: plus the LDS, its transposing reads and the lane exchanges, ``--lds mem,tr16,tr8,tr4,tr6,xlane``;
     ``mfma16``: plus the GEMMs again on the 16×16 instruction shapes, ``--mfma16 bf16,f16,i8,fp8,fp4``;
-    ``vmem``: plus the vector memory path, ``--vmem cache,sub,buf,dma``);
+    ``vmem``: plus the vector memory path, ``--vmem cache,sub,buf,dma``;
+    ``dcvt``: plus the decoding converters, ``--dcvt fp8,bf8,fp4,fp6,bf6``);
     non-zero exit keeps the pod in Init, and its JSON verdict is the container's termination message.  It asks for the same
     ``amd.com/gpu`` count as the notebook: the kubelet device manager hands an init
     container's devices on to the app containers, so the GPUs probed are the GPUs the
@@ -332,6 +342,8 @@ def gpu_probe_init_container(ngpu: int, env: Mapping[str, str] = os.environ, rcc
         args += ["--mfma16", GPU_PROBE_MFMA16_FORMATS]
     if vmem:  # after the --mfma16 arguments, for the same reason
         args += ["--vmem", GPU_PROBE_VMEM_FORMATS]
+    if dcvt:  # after the --vmem arguments, for the same reason
+        args += ["--dcvt", GPU_PROBE_DCVT_FORMATS]
     return {
         "name": GPU_PROBE_CONTAINER,
         "image": env.get("GPU_PROBE_IMAGE") or DEFAULT_GPU_PROBE_IMAGE,
@@ -356,7 +368,8 @@ def _gpu_probe(nb: dict, pod_spec: dict, env: Mapping[str, str]) -> None:
                                              dtypes=gpu_probe_dtypes(nb, env), mx_all=gpu_probe_mx_all(nb, env),
                                              fp=gpu_probe_fp(nb, env), sparse=gpu_probe_sparse(nb, env),
                                              cvt=gpu_probe_cvt(nb, env), lds=gpu_probe_lds(nb, env),
-                                             mfma16=gpu_probe_mfma16(nb, env), vmem=gpu_probe_vmem(nb, env)))
+                                             mfma16=gpu_probe_mfma16(nb, env), vmem=gpu_probe_vmem(nb, env),
+                                             dcvt=gpu_probe_dcvt(nb, env)))
 
 
 def generate_statefulset(nb: dict, is_generate_name: bool, env: Mapping[str, str] = os.environ) -> dict:

@@ -61,6 +61,10 @@ enum {
   ODH_CVT_BF16 = 5,  // bfloat16: no scale
   ODH_CVT_BLOCKS = 256,  // workgroups of the fused check: one per CU
   ODH_CVT_TABLE = 256,   // bytes of its scale table
+  // destination types of the decoding converters (gpu_probe_dcvt.h); their source formats are ODH_CVT_FP8 … ODH_CVT_FP4
+  ODH_DCVT_F32 = 0,   // float
+  ODH_DCVT_F16 = 1,   // IEEE half
+  ODH_DCVT_BF16 = 2,  // bfloat16
   // checks of the LDS step (gpu_probe_lds.h)
   ODH_LDS_MEM = 0,    // every dword of a CU's 160 KiB, written and read in different widths by different waves
   ODH_LDS_TR16 = 1,   // ds_read_b64_tr_b16
@@ -224,6 +228,23 @@ int odh_cvt_fill(int fmt, void* scale_table, hipStream_t stream);  // ODH_CVT_TA
 int odh_cvt_encode(int fmt, const float* x, const void* scales, void* codes, long rows, long K, hipStream_t stream);
 int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, long rows, long K, hipStream_t stream);
 int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream);
+// Decoding converters (fmt: ODH_CVT_FP8 … ODH_CVT_FP4, dst: ODH_DCVT_*; gpu_probe_dcvt.h): codes in the layout
+// odh_mx_gemm reads, 8-byte aligned, and scales [rows][K/32] E8M0 bytes to out [rows][K] f32 / f16 / bf16, 16-byte
+// aligned: value(code) · 2^(byte - 127) rounded to nearest even, subnormals kept; NaN codes and scale byte 255 give
+// NaN; K a multiple of 32, rows · K below 2^40.  The fused check: odh_dcvt_family_size values per wave, against
+// odh_dcvt_fill's table of ODH_CVT_TABLE scale bytes; counters as for the converters.  odh_dcvt_one: one wave, one
+// instruction; src 64 source registers (FP6 / BF6: 6 dwords per lane), scale 64 raw scale operands, both on the
+// device; form 0: the packed instruction, sel its word select (FP8, BF8: 0 … 1) or byte select (FP4: 0 … 3; FP6, BF6:
+// 0); form 1: the one-value form (FP8, BF8 to f32), sel its byte select 0 … 3; out: a lane's raw result registers,
+// 2 dwords (packed to f32), 1 (packed to f16 / bf16, one value), 32 or 16 (FP6 / BF6 to f32 or to f16 / bf16)
+unsigned odh_dcvt_family_size(int fmt);  // host only (0: no such format)
+unsigned long long odh_dcvt_fault_count(int fmt, int table_byte);  // host only: mismatches when that table byte is wrong
+int odh_dcvt_fill(int fmt, void* scale_table, hipStream_t stream);  // ODH_CVT_TABLE bytes
+int odh_dcvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream);
+int odh_dcvt_one(int fmt, int dst, int form, const uint32_t* src, const uint32_t* scale, int sel, void* out,
+                 hipStream_t stream);
+int odh_mx_dequantize(int fmt, int dst, const void* codes, const void* scales, void* out, long rows, long K,
+                      hipStream_t stream);
 // The LDS step (check: ODH_LDS_*; gpu_probe_lds.h).  table: ODH_LDS_TABLE bytes on the device, 4-byte aligned;
 // counters: ODH_NCOUNT × i32 of this check's own (slots as for the converters) and ODH_LDS_CU_WORDS dwords behind
 // them, the bitmap of the CUs the workgroups ran on.  odh_lds_tr_read: one wave, one transposing read; image

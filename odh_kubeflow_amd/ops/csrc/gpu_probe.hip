@@ -48,6 +48,10 @@
 //    v_cvt_pk_bf16_f32; gpu_probe_cvt.h): every rounding case of every code at every scale, on every SIMD,
 //    against codes known by construction; odh_cvt_family, the host's view of that family; and
 //    odh_cvt_quantize / odh_cvt_encode, f32 rows to OCP MX codes and scales in the layout odh_mx_gemm reads.
+//  * odh_dcvt_fill / odh_dcvt_probe_verify — the converters that decode such codes on the VALU
+//    (v_cvt_scalef32_pk_f32_fp8 and its kin to f32, f16 and bf16; gpu_probe_dcvt.h): every code in every source
+//    position through every select at every scale of the exact window; odh_dcvt_one, one such instruction on one
+//    wave; and odh_mx_dequantize, codes and scales back to rows: the inverse of odh_cvt_quantize.
 //  * odh_lds_fill / odh_lds_probe_verify — the LDS itself, the transposing LDS reads (ds_read_b64_tr_b16 / _b8 /
 //    _b4, ds_read_b96_tr_b6) and the lane exchanges (ds_bpermute, ds_swizzle, DPP, v_readlane, v_permlane32_swap and
 //    their kin; gpu_probe_lds.h), one workgroup per CU, against closed forms; odh_lds_cases and
@@ -74,6 +78,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 #include <utility>
 
 #include "gpu_probe.h"
@@ -857,6 +862,7 @@ int grid_for(size_t n, int per_block) {
 }
 
 #include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
+#include "gpu_probe_dcvt.h"  // the decoding converters (FP8, BF8, FP6, BF6, FP4 to f32, f16, bf16), on the converter kernels' helpers
 #include "gpu_probe_lds.h"  // the LDS, its transposing reads, the lane exchanges and the transposer of packed codes
 #include "gpu_probe_vmem.h"  // the vector memory path: caches, byte lanes, buffer descriptors, LDS-DMA loads, on the LDS step's helpers
 #include "gpu_probe_m16.h"  // the 16×16 matrix-core shapes (bf16, f16, i8, FP8, MXFP4), on the tile helpers, ring and tables above
@@ -1381,6 +1387,52 @@ int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStr
   unsigned* c = (unsigned*)counters;
   cvt_launch_probe(fmt, stream, (const uint8_t*)scale_table, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR,
                    c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ decoding converters (gpu_probe_dcvt.h)
+
+// host only (no HIP call): values one wave of the fused check compares (0: no such format), and the mismatches
+// of all waves when byte table_byte of the scale table is wrong: every non-zero code at that scale
+unsigned odh_dcvt_family_size(int fmt) { return dcvt_fmt_ok(fmt) ? dcvt_family_size(fmt) : 0u; }
+
+unsigned long long odh_dcvt_fault_count(int fmt, int table_byte) {
+  if (!dcvt_fmt_ok(fmt) || table_byte < 0 || table_byte >= ODH_CVT_TABLE) return 0ull;
+  return (unsigned long long)dcvt_fault_values(fmt, table_byte) * ODH_CVT_BLOCKS * 4;
+}
+
+int odh_dcvt_fill(int fmt, void* scale_table, hipStream_t stream) {
+  if (!dcvt_fmt_ok(fmt) || !scale_table) return (int)hipErrorInvalidValue;
+  dcvt_fill_kernel<<<1, ODH_CVT_TABLE, 0, stream>>>(fmt, (uint8_t*)scale_table);
+  return (int)hipGetLastError();
+}
+
+// every value of the family on every SIMD, against odh_dcvt_fill's table; counters is a counter block of this
+// format's own
+int odh_dcvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream) {
+  if (!dcvt_fmt_ok(fmt) || !scale_table || !counters) return (int)hipErrorInvalidValue;
+  unsigned* c = (unsigned*)counters;
+  dcvt_launch_probe(fmt, stream, (const uint8_t*)scale_table, counters + ODH_SLOT_XCD_BLOCKS, c + ODH_SLOT_GEMM_ERR,
+                    c + ODH_SLOT_ERR_XCD);
+  return (int)hipGetLastError();
+}
+
+// one wave, one instruction: the raw result registers
+int odh_dcvt_one(int fmt, int dst, int form, const uint32_t* src, const uint32_t* scale, int sel, void* out,
+                 hipStream_t stream) {
+  if (!dcvt_one_ok(fmt, dst, form, sel) || !src || !scale || !out || ((uintptr_t)src & 3) || ((uintptr_t)scale & 3) ||
+      ((uintptr_t)out & 3))
+    return (int)hipErrorInvalidValue;
+  dcvt_launch_one(fmt, stream, dst, form, sel, src, scale, (uint32_t*)out);
+  return (int)hipGetLastError();
+}
+
+// codes and E8M0 scales back to f32 / f16 / bf16 rows: the inverse of odh_cvt_quantize
+int odh_mx_dequantize(int fmt, int dst, const void* codes, const void* scales, void* out, long rows, long K,
+                      hipStream_t stream) {
+  if (!dcvt_rows_ok(fmt, dst, codes, scales, out, rows, K)) return (int)hipErrorInvalidValue;
+  const size_t n = dcvt_pieces(fmt, dst, rows, K);
+  dcvt_launch_rows(fmt, dst, grid_for(n, 1024), stream, codes, n, (const uint8_t*)scales, (u32x4*)out);
   return (int)hipGetLastError();
 }
 

@@ -66,6 +66,13 @@
 //      workgroup per CU on a 64 KiB slab of its own, compared in registers with closed forms (odh_vmem_probe_verify).
 //      The arena is the first 16 MiB of the sweep's buffer, which has been verified by then; a 1 KiB key table
 //      (odh_vmem_fill) and a counter block per check.  One entry for the whole step: "vmem":{"ok","errors","ms","bad"}.
+//  13. with --dcvt fp8,bf8,fp4,fp6,bf6 (the `amd.com/gpu-probe: "dcvt"` notebooks), after step 9, per format: the
+//      converters that decode those codes on the VALU (v_cvt_scalef32_pk_f32_fp8 and its kin, to f32, f16 and bf16:
+//      every weight-only-quantised GEMM prologue and FP8 / FP4 KV-cache read), every code in every source position
+//      through every select at every scale of the exact window on every SIMD, compared in registers with bits known
+//      by construction, NaN and infinity codes by their class (odh_dcvt_probe_verify); bf8 to f16 has no exact window,
+//      so v_cvt_scalef32_pk_f16_bf8 alone is not issued: a 256-byte scale table (odh_dcvt_fill) and a counter block per
+//      format.  One entry for the whole step: "dcvt":{"ok","errors","ms","bad"}.
 //
 // All devices are launched before any is waited on.  The result is one compact JSON object
 // (<4 KiB: the kubelet's termination-message limit) written to --json (default
@@ -160,8 +167,8 @@ struct Step {
   }
 };
 
-Prepare mx_prepare, dt_prepare, fp_prepare, sp_prepare, cvt_prepare, lds_prepare, m16_prepare, vmem_prepare;
-Check mx_check, dt_check, fp_check, sp_check, cvt_check, lds_check, m16_check, vmem_check;
+Prepare mx_prepare, dt_prepare, fp_prepare, sp_prepare, cvt_prepare, lds_prepare, m16_prepare, vmem_prepare, dcvt_prepare;
+Check mx_check, dt_check, fp_check, sp_check, cvt_check, lds_check, m16_check, vmem_check, dcvt_check;
 int lds_blocks(int, int, int) { return ODH_LDS_BLOCKS; }
 int cvt_blocks(int, int, int) { return ODH_CVT_BLOCKS; }
 int vmem_blocks(int, int, int) { return ODH_VM_BLOCKS; }
@@ -169,9 +176,10 @@ int vmem_blocks(int, int, int) { return ODH_VM_BLOCKS; }
 double cvt_work(int fmt) { return (double)odh_cvt_family_size(fmt) * ODH_CVT_BLOCKS * 4; }
 
 // the steps in the verdict's order, which is also the order of their counter blocks and events
-enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM, N_STEPS };
+enum { STEP_MX, STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM, STEP_DCVT, N_STEPS };
 // the order they run in
-constexpr int RUN_ORDER[N_STEPS] = {STEP_DTYPES, STEP_FP, STEP_SPARSE, STEP_MX, STEP_CVT, STEP_LDS, STEP_MFMA16, STEP_VMEM};
+constexpr int RUN_ORDER[N_STEPS] = {STEP_DTYPES, STEP_FP,  STEP_SPARSE, STEP_MX,  STEP_CVT,
+                                    STEP_DCVT,   STEP_LDS, STEP_MFMA16, STEP_VMEM};
 
 struct Options {
   int M = 4096, N = 4096, K = 1024;
@@ -215,6 +223,14 @@ struct Options {
        // most 19, an error string of up to 120) it is 4158, which does not: the assembled verdict then, and only
        // then, goes without its setup_ms object (at least 86 bytes: 4072).  See fit_verdict
        vmem_prepare, vmem_check, vmem_blocks, nullptr, "", false, true, ODH_NCOUNT + ODH_LDS_CU_WORDS},
+      {"dcvt", "decode",
+       {{"fp8", ODH_CVT_FP8}, {"bf8", ODH_CVT_BF8}, {"fp4", ODH_CVT_FP4}, {"fp6", ODH_CVT_FP6}, {"bf6", ODH_CVT_BF6}},
+       // flat once more.  The entry ,"dcvt":{"ok":true,"errors":0,"ms":99.999,"bad":""} is 51 bytes and "dcvt":99.999, in
+       // timings_ms 14: the widest healthy verdict of 8 GPUs with every step grows from 4009 to 4074, which fits the
+       // kubelet's 4096.  With one failing step (4158 before this step) it is 4223, and 4137 without setup_ms, which
+       // no longer fits: such a verdict keeps every step's entry and the error string and goes without the rest of
+       // its timings too (timings_ms keeps its total; at least 280 bytes less).  See fit_verdict
+       dcvt_prepare, dcvt_check, cvt_blocks, nullptr, "", false, true},
   };
   bool quiet = false;
   // streams created per device: 0 = the device's null stream (nothing created; the default),
@@ -252,6 +268,8 @@ struct Dev {
   void* lds_table = nullptr;
   // --vmem: the same behind that
   void* vmem_table = nullptr;
+  // --dcvt: its scale table behind that
+  void* dcvt_table = nullptr;
   // per step, one per asked-for format: counter blocks behind the first, in the counters region
   std::vector<Slot> slots[N_STEPS];
   std::string error;
@@ -265,6 +283,7 @@ int usage(const char* argv0) {
                "[--timeout-ms N] [--streams 0|1|2] [--inject-fault gemm|hbm|xgmi|rccl|mx|dtypes|fp] "
                "[--inject-fault sparse] [--inject-fault cvt] [--inject-fault lds] [--quiet] "
                "[--vmem cache,sub,buf,dma] [--inject-fault vmem] "
+               "[--dcvt fp8,bf8,fp4,fp6,bf6] [--inject-fault dcvt] "
                "[--mfma16 bf16,f16,i8,fp8,fp4] [--inject-fault mfma16]\n",
                argv0);
   return 64;
@@ -420,13 +439,14 @@ bool setup_alloc(Dev& d, const Options& o) {
   // both operands and the table, --dtypes nothing else: its operands are no larger; --fp widens the operands;
   // --sparse adds the metadata and its table (compressed A and Bt are no larger than the bf16 operands);
   // --cvt adds its scale table; --lds its key table; --mfma16, for fp8 or fp4, the scales and table of --mx;
-  // --vmem a key table as --lds (its arena is the sweep's buffer)
+  // --vmem a key table as --lds (its arena is the sweep's buffer); --dcvt a scale table as --cvt
   size_t ncount = ODH_NCOUNT;  // ints of the counters region
   for (const Step& s : o.steps) ncount += s.block * s.asked.size();
   bool mx = !o.steps[STEP_MX].asked.empty();  // whether any step needs the MX scales and table
   for (int fmt : o.steps[STEP_MFMA16].asked) mx = mx || fmt == ODH_M16_FP8 || fmt == ODH_M16_FP4;
   const bool sparse = !o.steps[STEP_SPARSE].asked.empty(), cvt = !o.steps[STEP_CVT].asked.empty();
   const bool lds = !o.steps[STEP_LDS].asked.empty(), vmem = !o.steps[STEP_VMEM].asked.empty();
+  const bool dcvt = !o.steps[STEP_DCVT].asked.empty();
   const size_t esz = operand_esize(o);
   const size_t at_a = take((size_t)o.M * o.K * esz), at_bt = take((size_t)o.N * o.K * esz), at_hbm = take(o.hbm_bytes);
   const size_t at_tile_xcd = take(sizeof(int) * (size_t)(o.M / 128) * (o.N / 128));
@@ -438,6 +458,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   const size_t at_cvt_table = cvt ? take(ODH_CVT_TABLE) : 0;
   const size_t at_lds_table = lds ? take(ODH_LDS_TABLE) : 0;
   const size_t at_vmem_table = vmem ? take(ODH_VM_TABLE) : 0;
+  const size_t at_dcvt_table = dcvt ? take(ODH_CVT_TABLE) : 0;
   HIP_TRY(hipMalloc(&d.block, total));
   d.malloc_ms = ms_since(t0);
   char* p = (char*)d.block;
@@ -458,6 +479,7 @@ bool setup_alloc(Dev& d, const Options& o) {
   if (cvt) d.cvt_table = p + at_cvt_table;
   if (lds) d.lds_table = p + at_lds_table;
   if (vmem) d.vmem_table = p + at_vmem_table;
+  if (dcvt) d.dcvt_table = p + at_dcvt_table;
   int* block = d.counters + ODH_NCOUNT;
   for (int s = 0; s < N_STEPS; ++s) {
     d.slots[s].resize(o.steps[s].asked.size());
@@ -629,6 +651,19 @@ bool cvt_prepare(Dev& d, const Options&, int fmt, bool fault) {
 }
 bool cvt_check(Dev& d, const Options&, int fmt, int* counters) {
   HIP_TRY(odh_cvt_probe_verify(fmt, d.cvt_table, counters, d.sh));
+  return true;
+}
+
+// a format of --dcvt, after --cvt: its scale table, then the fused check of its decoding converters.  Only the first
+// asked-for format is faulted: entry 3 of the table becomes 0 (the fill has at least 5 there), so every non-zero
+// code at that scale gets another exponent: odh_dcvt_fault_count(fmt, 3) values
+bool dcvt_prepare(Dev& d, const Options& o, int fmt, bool fault) {
+  HIP_TRY(odh_dcvt_fill(fmt, d.dcvt_table, d.sh));
+  if (fault && fmt == o.steps[STEP_DCVT].asked[0]) HIP_TRY(hipMemsetAsync((char*)d.dcvt_table + 3, 0, 1, d.sh));
+  return true;
+}
+bool dcvt_check(Dev& d, const Options&, int fmt, int* counters) {
+  HIP_TRY(odh_dcvt_probe_verify(fmt, d.dcvt_table, counters, d.sh));
   return true;
 }
 
@@ -1042,13 +1077,19 @@ std::string steps_json(std::vector<Dev>& devs, const Options& o, const std::vect
 
 // The kubelet keeps 4096 bytes of a termination message.  Every verdict the program could emit before --vmem fits
 // with setup_ms and is unchanged; one that would not fit goes without setup_ms (the arithmetic is at the vmem
-// step), and should even that be too long (it cannot be with the steps there are), the short form of a failure
-// with the first error is sent, so that what arrives is always whole JSON
+// step); one that still does not fit keeps every step's entry and the first error string and goes without the
+// rest of its timings as well, timings_ms holding only its total (the arithmetic is at the dcvt step); and should
+// even that be too long (it cannot be with the steps there are), the short form of a failure with the first
+// error is sent, so that what arrives is always whole JSON
 std::string fit_verdict(const std::string& head, const char* setup, const char* tail, bool ok, int ndev,
                         const std::string& first_err, Clock::time_point t_start) {
   constexpr size_t LIMIT = 4096;
   std::string json = head + setup + tail;
   if (json.size() > LIMIT) json = head + tail;
+  if (json.size() > LIMIT) {
+    const char* total = std::strstr(tail, "\"total\":");  // the last entry of timings_ms, up to the closing braces
+    json = head + ",\"timings_ms\":{" + (total ? total : "}}");
+  }
   if (json.size() > LIMIT)
     json = ok ? std::string("{\"ok\":true,\"devices\":") + std::to_string(ndev) + tail
               : fail_json("check failed", first_err, ms_since(t_start));

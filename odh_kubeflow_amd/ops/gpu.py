@@ -39,6 +39,12 @@
   (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
   layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
   (``odh-gpu-probe --cvt``); :func:`cvt_family` is that check's family of inputs and expected codes.
+* :func:`mx_dequantize`, :func:`dcvt_one`, :func:`dcvt_probe` (with :func:`dcvt_fill`, :func:`dcvt_verify`,
+  :func:`dcvt_fault_count`) — the hardware converters that decode those codes on the VALU
+  (``v_cvt_scalef32_pk_f32_fp8`` and its kin, to float32, float16 and bfloat16): codes and E8M0 scales back to rows,
+  the inverse of :func:`mx_quantize`; one such instruction on one wave; and the exact check of every code in every
+  source position at every scale of the exact window (``odh-gpu-probe --dcvt``; ``bf8`` to float16 has no such
+  window, so the step issues fourteen of the fifteen instructions).
 * :func:`probe_devices` / :func:`xgmi_ring_check` — the same harness over several GPUs; a link is
   :func:`link_check` of two probes, against :attr:`GpuProbe.pattern_seed` (the seed of the pattern the source's
   buffer holds, whichever path wrote it), and two probes on one GPU make a link too.
@@ -126,6 +132,10 @@ ODH_CVT_FP4 = 4  # e2m1
 ODH_CVT_BF16 = 5  # bfloat16: no scale
 ODH_CVT_BLOCKS = 256  # workgroups of the fused check: one per CU
 ODH_CVT_TABLE = 256  # bytes of its scale table
+# destination types of the decoding converters (csrc/gpu_probe_dcvt.h); their source formats are the scaled ODH_CVT_* ones
+ODH_DCVT_F32 = 0  # float
+ODH_DCVT_F16 = 1  # IEEE half
+ODH_DCVT_BF16 = 2  # bfloat16
 CVT_FORMATS = {"fp8": ODH_CVT_FP8, "bf8": ODH_CVT_BF8, "fp4": ODH_CVT_FP4, "fp6": ODH_CVT_FP6, "bf6": ODH_CVT_BF6,
                "bf16": ODH_CVT_BF16}  # what ``--cvt`` checks, in its order
 
@@ -276,6 +286,13 @@ SIGNATURES = {
     "odh_cvt_encode": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_quantize": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_probe_verify": (_i, [_i, _vp, _vp, _vp]),
+    # decoding converters (csrc/gpu_probe_dcvt.h)
+    "odh_dcvt_family_size": (_u32, [_i]),
+    "odh_dcvt_fault_count": (ctypes.c_ulonglong, [_i, _i]),
+    "odh_dcvt_fill": (_i, [_i, _vp, _vp]),
+    "odh_dcvt_probe_verify": (_i, [_i, _vp, _vp, _vp]),
+    "odh_dcvt_one": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "odh_mx_dequantize": (_i, [_i, _i, _vp, _vp, _vp, _long, _long, _vp]),
     # the LDS step and the transposer of packed codes (csrc/gpu_probe_lds.h)
     "odh_lds_cases": (ctypes.c_ulonglong, [_i]),
     "odh_lds_fault_count": (ctypes.c_ulonglong, [_i, _i]),
@@ -1068,13 +1085,11 @@ def cvt_fill(fmt, table) -> None:
     _check(load_library().odh_cvt_fill(code, table.data_ptr(), _stream_ptr(table.device)))
 
 
-def cvt_verify(fmt, table) -> dict:
-    """The fused check against ``table`` on a fresh counter block: every wave of ``ODH_CVT_BLOCKS`` workgroups
-    converts the whole family.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms``, and ``gcvt_s``, family cases
-    per nanosecond over all waves."""
+def _cvt_fused(entry, family: int, code: int, table) -> dict:
+    """A fused converter check (``entry``: the library's ``odh_cvt_probe_verify`` or ``odh_dcvt_probe_verify``) of
+    format ``code`` against ``table`` on a fresh counter block, and its report; ``family``: values a wave handles."""
     import torch
 
-    code = _cvt_format(fmt)
     if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_CVT_TABLE,) or not table.is_cuda \
             or not table.is_contiguous():
         raise ValueError(f"table must be a contiguous uint8 [{ODH_CVT_TABLE}] tensor on a GPU")
@@ -1083,7 +1098,7 @@ def cvt_verify(fmt, table) -> dict:
         counters = torch.zeros((ODH_NCOUNT,), dtype=torch.int32, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _check(load_library().odh_cvt_probe_verify(code, table.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
+        _check(entry(code, table.data_ptr(), counters.data_ptr(), _stream_ptr(dev)))
         e1.record()
         e1.synchronize()
         h = counters.cpu().tolist()
@@ -1092,8 +1107,16 @@ def cvt_verify(fmt, table) -> dict:
         "errors": h[ODH_SLOT_GEMM_ERR] & 0xFFFFFFFF,
         "err_xcd": [x & 0xFFFFFFFF for x in h[ODH_SLOT_ERR_XCD:ODH_SLOT_ERR_XCD + ODH_N_XCD]],
         "xcd_blocks": h[ODH_SLOT_XCD_BLOCKS:ODH_SLOT_XCD_BLOCKS + ODH_N_XCD],
-        "ms": ms, "gcvt_s": cvt_family_size(code) * ODH_CVT_BLOCKS * 4 / (ms * 1e6) if ms > 0 else 0.0,
+        "ms": ms, "gcvt_s": family * ODH_CVT_BLOCKS * 4 / (ms * 1e6) if ms > 0 else 0.0,
     }
+
+
+def cvt_verify(fmt, table) -> dict:
+    """The fused check against ``table`` on a fresh counter block: every wave of ``ODH_CVT_BLOCKS`` workgroups
+    converts the whole family.  ``errors``, ``err_xcd``, ``xcd_blocks``, ``ms``, and ``gcvt_s``, family cases
+    per nanosecond over all waves."""
+    code = _cvt_format(fmt)
+    return _cvt_fused(load_library().odh_cvt_probe_verify, cvt_family_size(code), code, table)
 
 
 def cvt_probe(device: int, fmt) -> dict:
@@ -1106,6 +1129,124 @@ def cvt_probe(device: int, fmt) -> dict:
         table = torch.empty((ODH_CVT_TABLE,), dtype=torch.uint8, device=dev)
         cvt_fill(code, table)
         return cvt_verify(code, table)
+
+
+DCVT_FORMATS = {"fp8": ODH_CVT_FP8, "bf8": ODH_CVT_BF8, "fp4": ODH_CVT_FP4, "fp6": ODH_CVT_FP6,
+                "bf6": ODH_CVT_BF6}  # what ``--dcvt`` checks, in its order
+
+
+def _dcvt_format(fmt) -> int:
+    code = DCVT_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    if isinstance(code, bool) or code not in DCVT_FORMATS.values():
+        raise ValueError(f"source format must be one of {sorted(DCVT_FORMATS)}; got {fmt!r}")
+    return code
+
+
+def _dcvt_dst(dtype) -> int:
+    import torch
+
+    dst = {torch.float32: ODH_DCVT_F32, torch.float16: ODH_DCVT_F16, torch.bfloat16: ODH_DCVT_BF16}.get(dtype)
+    if dst is None:
+        raise ValueError(f"the destination must be float32, float16 or bfloat16; got {dtype!r}")
+    return dst
+
+
+def mx_dequantize(fmt, codes, scales, dtype=None):
+    """The inverse of :func:`mx_quantize` on the GPU: ``codes`` uint8 ``[rows, mx_row_bytes(fmt, K)]`` in the layout
+    :func:`mx_gemm` reads and E8M0 ``scales`` uint8 ``[rows, K/32]`` to a ``[rows, K]`` tensor of ``dtype`` (float32
+    by default, float16 or bfloat16), through the hardware's decoding converters.
+
+    For every code and every scale byte 0 … 254 an element is ``value(code) · 2^(byte - 127)`` rounded to nearest
+    even into ``dtype``: exact wherever it is representable, subnormal results kept, float16 overflow to the
+    infinity of that sign, ``-0`` stays ``-0``.  An fp8 or bf8 NaN code gives a NaN, bf8's infinities stay
+    infinities at every scale, and scale byte 255 (the E8M0 NaN) makes every element of its block NaN."""
+    import torch
+
+    code, dst = _dcvt_format(fmt), _dcvt_dst(torch.float32 if dtype is None else dtype)
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError("the decoding converters take uint8 codes and uint8 scales")
+    if codes.dim() != 2 or not codes.is_cuda or not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous 2-D tensor on a GPU")
+    rows, row_bytes = codes.shape
+    _, num, den = _MX_LAYOUT[code]
+    k = row_bytes // num * den
+    if rows < 1 or k < 32 or k % 32 or mx_row_bytes(code, k) != row_bytes:
+        raise ValueError(f"codes must be [rows >= 1, mx_row_bytes of a positive multiple of 32]; got {tuple(codes.shape)}")
+    if codes.data_ptr() % 8:
+        raise ValueError("codes must be 8-byte aligned")
+    if not scales.is_cuda or scales.device != codes.device or not scales.is_contiguous() \
+            or tuple(scales.shape) != (rows, k // 32):
+        raise ValueError(f"scales must be a contiguous [{rows},{k // 32}] tensor on the codes' GPU")
+    out = torch.empty((rows, k), dtype=torch.float32 if dtype is None else dtype, device=codes.device)
+    _check(load_library().odh_mx_dequantize(code, dst, codes.data_ptr(), scales.data_ptr(), out.data_ptr(), rows, k,
+                                            _stream_ptr(codes.device)))
+    return out
+
+
+def dcvt_one(fmt, dtype, src, scale, sel: int = 0, form: int = 0):
+    """One wave, one decoding instruction: lane ``l`` converts its source register ``src[l]`` (int32 ``[64]`` on a
+    GPU; fp6 / bf6: ``[64, 6]``, 24 bytes per lane) with the raw float32 scale operand ``scale[l]`` (int32 ``[64]``:
+    the bits; an E8M0 byte shifted left by 23).  ``form`` 0 is the packed instruction and ``sel`` its word select
+    (fp8, bf8: 0 … 1) or byte select (fp4: 0 … 3); ``form`` 1 the one-value form (fp8 / bf8 to float32) and ``sel`` its
+    byte select.  Returns the raw result registers, int32 ``[64, W]``: W = 2 (packed to float32), 1 (packed to
+    float16 / bfloat16: the first value in the low half; one value), 32 or 16 (fp6 / bf6)."""
+    import torch
+
+    code, dst = _dcvt_format(fmt), _dcvt_dst(dtype)
+    six = code in (ODH_CVT_FP6, ODH_CVT_BF6)
+    for t, shape, what in ((src, (64, 6) if six else (64,), "src"), (scale, (64,), "scale")):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous int32 {list(shape)} tensor on a GPU")
+    if scale.device != src.device:
+        raise ValueError("src and scale must be on one GPU")
+    words = (32 if dst == ODH_DCVT_F32 else 16) if six else 1 if form == 1 or dst != ODH_DCVT_F32 else 2
+    out = torch.empty((64, words), dtype=torch.int32, device=src.device)
+    _check(load_library().odh_dcvt_one(code, dst, form, src.data_ptr(), scale.data_ptr(), sel, out.data_ptr(),
+                                       _stream_ptr(src.device)))
+    return out
+
+
+def dcvt_family_size(fmt) -> int:
+    """Values one wave of the fused decoding check compares.  Host arithmetic only."""
+    return load_library().odh_dcvt_family_size(_dcvt_format(fmt))
+
+
+def dcvt_fault_count(fmt, table_byte: int) -> int:
+    """Mismatches the fused check counts when byte ``table_byte`` of its scale table is wrong: every finite non-zero code
+    of every destination whose window holds that scale, on every wave (0 for an unknown format or a byte the check
+    does not read).  Host arithmetic only."""
+    code = DCVT_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+    return load_library().odh_dcvt_fault_count(code if isinstance(code, int) else -1, table_byte)
+
+
+def dcvt_fill(fmt, table) -> None:
+    """The scale table of the fused decoding check (``ODH_CVT_TABLE`` uint8) written into ``table``."""
+    import torch
+
+    code = _dcvt_format(fmt)
+    if table.dtype != torch.uint8 or tuple(table.shape) != (ODH_CVT_TABLE,) or not table.is_cuda \
+            or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 [{ODH_CVT_TABLE}] tensor on a GPU")
+    _check(load_library().odh_dcvt_fill(code, table.data_ptr(), _stream_ptr(table.device)))
+
+
+def dcvt_verify(fmt, table) -> dict:
+    """The fused check against ``table`` on a fresh counter block: every wave of ``ODH_CVT_BLOCKS`` workgroups
+    decodes the whole family.  The dict of :func:`cvt_verify`; ``gcvt_s`` counts compared values."""
+    code = _dcvt_format(fmt)
+    return _cvt_fused(load_library().odh_dcvt_probe_verify, dcvt_family_size(code), code, table)
+
+
+def dcvt_probe(device: int, fmt) -> dict:
+    """One decoding-converter probe of a GPU: the scale table, then the fused check.  The dict of :func:`dcvt_verify`."""
+    import torch
+
+    code = _dcvt_format(fmt)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        table = torch.empty((ODH_CVT_TABLE,), dtype=torch.uint8, device=dev)
+        dcvt_fill(code, table)
+        return dcvt_verify(code, table)
 
 
 def _lds_check(check) -> int:
