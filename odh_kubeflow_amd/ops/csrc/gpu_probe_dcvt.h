@@ -51,7 +51,8 @@
 // bytes, each of the fifteen instructions gives exactly what the contract asks: subnormal results kept, rounding to
 // nearest even into f16 / bf16, overflow to infinity, NaN codes to NaN, bf8 infinities kept, byte 0 as 2^-127 and
 // byte 255 as NaN; mantissa and sign of the scale operand are ignored.  The operation is a function of one code and
-// one scale byte, so that measurement covers all of its inputs; tests/test_gpu_dcvt.py holds it to the reference.
+// one scale byte, so that measurement covers all of its inputs; tests/test_gpu_dcvt_edges.py repeats it with every
+// suite: every code at every scale byte in every position of a lane's load, against the reference.
 
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(32))) float f32x32;
