@@ -46,7 +46,8 @@ def targets() -> Dict[str, dict]:
                      os.path.join(CSRC, "gpu_probe_dense.h"), os.path.join(CSRC, "gpu_probe_fp.h"),
                      os.path.join(CSRC, "gpu_probe_sparse.h"), os.path.join(CSRC, "gpu_probe_cvt.h"),
                      os.path.join(CSRC, "gpu_probe_lds.h"), os.path.join(CSRC, "gpu_probe_m16.h"),
-                     os.path.join(CSRC, "gpu_probe_vmem.h"), os.path.join(CSRC, "gpu_probe_dcvt.h")],
+                     os.path.join(CSRC, "gpu_probe_vmem.h"), os.path.join(CSRC, "gpu_probe_dcvt.h"),
+                     os.path.join(CSRC, "gpu_probe_cvt16.h")],
             "cmd": lambda src, out: [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
                                      *src, "-o", out],
         },

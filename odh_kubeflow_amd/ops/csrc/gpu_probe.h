@@ -228,6 +228,13 @@ int odh_cvt_fill(int fmt, void* scale_table, hipStream_t stream);  // ODH_CVT_TA
 int odh_cvt_encode(int fmt, const float* x, const void* scales, void* codes, long rows, long K, hipStream_t stream);
 int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, long rows, long K, hipStream_t stream);
 int odh_cvt_probe_verify(int fmt, const void* scale_table, int* counters, hipStream_t stream);
+// The same two from 16-bit rows (gpu_probe_cvt16.h): x [rows][K] bfloat16 or float16 (src: ODH_DCVT_BF16 /
+// ODH_DCVT_F16), fmt ODH_CVT_FP8 … ODH_CVT_FP4.  odh_cvt_quantize16 gives, byte for byte, what odh_cvt_quantize gives
+// for the widened values.  FP6 / BF6 codes 16-byte aligned, scales never null, rows · K below 2^40
+int odh_cvt_encode16(int fmt, int src, const void* x, const void* scales, void* codes, long rows, long K,
+                     hipStream_t stream);
+int odh_cvt_quantize16(int fmt, int src, const void* x, void* codes, void* scales_out, long rows, long K,
+                       hipStream_t stream);
 // Decoding converters (fmt: ODH_CVT_FP8 … ODH_CVT_FP4, dst: ODH_DCVT_*; gpu_probe_dcvt.h): codes in the layout
 // odh_mx_gemm reads, 8-byte aligned, and scales [rows][K/32] E8M0 bytes to out [rows][K] f32 / f16 / bf16, 16-byte
 // aligned: value(code) · 2^(byte - 127) rounded to nearest even, subnormals kept; NaN codes and scale byte 255 give

@@ -47,7 +47,10 @@
 //    (v_cvt_scalef32_pk_fp8_f32 / _bf8_f32 / _fp4_f32, v_cvt_scalef32_2xpk16_fp6_f32 / _bf6_f32,
 //    v_cvt_pk_bf16_f32; gpu_probe_cvt.h): every rounding case of every code at every scale, on every SIMD,
 //    against codes known by construction; odh_cvt_family, the host's view of that family; and
-//    odh_cvt_quantize / odh_cvt_encode, f32 rows to OCP MX codes and scales in the layout odh_mx_gemm reads.
+//    odh_cvt_quantize / odh_cvt_encode, f32 rows to OCP MX codes and scales in the layout odh_mx_gemm reads;
+//    odh_cvt_quantize16 / odh_cvt_encode16, the same from bfloat16 / float16 rows on the 16-bit-source converters
+//    (v_cvt_scalef32_pk_fp8_bf16 / _f16 and their bf8, fp4, pk32_fp6 and pk32_bf6 kin; gpu_probe_cvt16.h), the
+//    6-bit formats regrouped through LDS.
 //  * odh_dcvt_fill / odh_dcvt_probe_verify — the converters that decode such codes on the VALU
 //    (v_cvt_scalef32_pk_f32_fp8 and its kin to f32, f16 and bf16; gpu_probe_dcvt.h): every code in every source
 //    position through every select at every scale of the exact window; odh_dcvt_one, one such instruction on one
@@ -863,6 +866,7 @@ int grid_for(size_t n, int per_block) {
 
 #include "gpu_probe_cvt.h"  // the converter kernels (FP8, BF8, FP6, BF6, FP4, bf16), on xcc_id and the sweep's slabs
 #include "gpu_probe_dcvt.h"  // the decoding converters (FP8, BF8, FP6, BF6, FP4 to f32, f16, bf16), on the converter kernels' helpers
+#include "gpu_probe_cvt16.h"  // the quantiser for bfloat16 / float16 rows, on the 16-bit-source converters and both headers' helpers
 #include "gpu_probe_lds.h"  // the LDS, its transposing reads, the lane exchanges and the transposer of packed codes
 #include "gpu_probe_vmem.h"  // the vector memory path: caches, byte lanes, buffer descriptors, LDS-DMA loads, on the LDS step's helpers
 #include "gpu_probe_m16.h"  // the 16×16 matrix-core shapes (bf16, f16, i8, FP8, MXFP4), on the tile helpers, ring and tables above
@@ -1377,6 +1381,25 @@ int odh_cvt_quantize(int fmt, const float* x, void* codes, void* scales_out, lon
   const size_t n = cvt_pieces(fmt, rows, K);
   cvt_launch_rows<true>(fmt, grid_for(n, 1024), stream, (const cvt_f4*)x, n, (const uint8_t*)nullptr, codes,
                         (uint8_t*)scales_out);
+  return (int)hipGetLastError();
+}
+
+// the same two for bfloat16 / float16 rows (src: ODH_DCVT_BF16 / ODH_DCVT_F16; gpu_probe_cvt16.h), scaled formats only
+int odh_cvt_encode16(int fmt, int src, const void* x, const void* scales, void* codes, long rows, long K,
+                     hipStream_t stream) {
+  if (!cvt16_rows_ok(fmt, src, x, codes, scales, rows, K)) return (int)hipErrorInvalidValue;
+  const size_t n = (size_t)rows * (size_t)K / 8;  // 16-byte pieces of x
+  cvt16_launch_rows<false>(fmt, src, grid_for(n, 1024), stream, (const u32x4*)x, n, (const uint8_t*)scales, codes,
+                           (uint8_t*)nullptr);
+  return (int)hipGetLastError();
+}
+
+int odh_cvt_quantize16(int fmt, int src, const void* x, void* codes, void* scales_out, long rows, long K,
+                       hipStream_t stream) {
+  if (!cvt16_rows_ok(fmt, src, x, codes, scales_out, rows, K)) return (int)hipErrorInvalidValue;
+  const size_t n = (size_t)rows * (size_t)K / 8;
+  cvt16_launch_rows<true>(fmt, src, grid_for(n, 1024), stream, (const u32x4*)x, n, (const uint8_t*)nullptr, codes,
+                          (uint8_t*)scales_out);
   return (int)hipGetLastError();
 }
 

@@ -38,7 +38,9 @@
 * :func:`mx_quantize`, :func:`cvt_encode`, :func:`cvt_probe` — the hardware converters that make those codes
   (``v_cvt_scalef32_pk_fp8_f32`` and its kin, ``v_cvt_pk_bf16_f32``): OCP MX quantisation of float32 rows into the
   layout :func:`mx_gemm` reads, the bare instruction, and the exact check of every rounding case on every SIMD
-  (``odh-gpu-probe --cvt``); :func:`cvt_family` is that check's family of inputs and expected codes.
+  (``odh-gpu-probe --cvt``); :func:`cvt_family` is that check's family of inputs and expected codes.  bfloat16 and
+  float16 rows go through the converters that read 16-bit sources (``v_cvt_scalef32_pk_fp8_bf16`` / ``_f16`` and
+  their bf8, fp4, ``pk32_fp6`` and ``pk32_bf6`` kin) and give what their float32 copy would, without that copy.
 * :func:`mx_dequantize`, :func:`dcvt_one`, :func:`dcvt_probe` (with :func:`dcvt_fill`, :func:`dcvt_verify`,
   :func:`dcvt_fault_count`) — the hardware converters that decode those codes on the VALU
   (``v_cvt_scalef32_pk_f32_fp8`` and its kin, to float32, float16 and bfloat16): codes and E8M0 scales back to rows,
@@ -286,6 +288,8 @@ SIGNATURES = {
     "odh_cvt_encode": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_quantize": (_i, [_i, _vp, _vp, _vp, _long, _long, _vp]),
     "odh_cvt_probe_verify": (_i, [_i, _vp, _vp, _vp]),
+    "odh_cvt_encode16": (_i, [_i, _i, _vp, _vp, _vp, _long, _long, _vp]),
+    "odh_cvt_quantize16": (_i, [_i, _i, _vp, _vp, _vp, _long, _long, _vp]),
     # decoding converters (csrc/gpu_probe_dcvt.h)
     "odh_dcvt_family_size": (_u32, [_i]),
     "odh_dcvt_fault_count": (ctypes.c_ulonglong, [_i, _i]),
@@ -999,14 +1003,17 @@ def cvt_family(fmt, first: int = 0, n: Optional[int] = None) -> dict:
 
 
 def _cvt_rows(fmt, x, scales=None):
-    """Checks of the converter entry points, before launch: ``x`` float32 ``[rows, K]`` on a GPU, contiguous,
-    16-byte aligned, K a multiple of 32; ``scales`` (if given) uint8 ``[rows, K/32]`` on the same GPU.
-    Returns the format code, rows, K."""
+    """Checks of the converter entry points, before launch: ``x`` float32, bfloat16 or float16 ``[rows, K]`` on a
+    GPU, contiguous, 16-byte aligned, K a multiple of 32; ``scales`` (if given) uint8 ``[rows, K/32]`` on the same
+    GPU.  Returns the format code, the source type's ``ODH_DCVT_*`` code, rows, K."""
     import torch
 
     code = _cvt_format(fmt)
-    if x.dtype != torch.float32 or (scales is not None and scales.dtype != torch.uint8):
-        raise ValueError("the converters take float32 values and uint8 scales")
+    src = {torch.float32: ODH_DCVT_F32, torch.bfloat16: ODH_DCVT_BF16, torch.float16: ODH_DCVT_F16}.get(x.dtype)
+    if src is None or (scales is not None and scales.dtype != torch.uint8):
+        raise ValueError("the converters take float32, bfloat16 or float16 values and uint8 scales")
+    if code == ODH_CVT_BF16 and src != ODH_DCVT_F32:
+        raise ValueError("bf16 is made of float32 values only")
     if x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
         raise ValueError("x must be a contiguous 2-D tensor on a GPU")
     rows, k = x.shape
@@ -1020,7 +1027,7 @@ def _cvt_rows(fmt, x, scales=None):
         if not scales.is_cuda or scales.device != x.device or not scales.is_contiguous() \
                 or tuple(scales.shape) != (rows, k // 32):
             raise ValueError(f"scales must be a contiguous [{rows},{k // 32}] tensor on x's GPU")
-    return code, rows, k
+    return code, src, rows, k
 
 
 def _cvt_out(code: int, x, rows: int, k: int):
@@ -1035,11 +1042,20 @@ def cvt_encode(fmt, x, scales=None):
     """The hardware converter as it is: ``x`` ``[rows, K]`` float32 divided by the caller's E8M0 ``scales``
     ``[rows, K/32]`` and rounded to nearest even, to uint8 codes in the layout :func:`mx_gemm` reads
     (``[rows, mx_row_bytes]``); what lies beyond the largest finite value becomes what the instruction makes
-    of it.  ``"bf16"`` takes no scales and returns a bfloat16 ``[rows, K]`` tensor."""
-    code, rows, k = _cvt_rows(fmt, x, scales)
+    of it.  ``"bf16"`` takes no scales and returns a bfloat16 ``[rows, K]`` tensor.
+
+    A bfloat16 or float16 ``x`` goes to the scaled formats through the instruction of its own type
+    (``v_cvt_scalef32_pk_fp8_bf16`` and its kin), not through a float32 copy: for finite values whose quotient
+    does not exceed the largest finite value that is the quotient of the widened value rounded to nearest even,
+    beyond it whatever that instruction gives.  ``"bf16"`` of a 16-bit ``x`` is refused."""
+    code, src, rows, k = _cvt_rows(fmt, x, scales)
     if code != ODH_CVT_BF16 and scales is None:
         raise ValueError("the scaled formats need scales")
     out = _cvt_out(code, x, rows, k)
+    if src != ODH_DCVT_F32:
+        _check(load_library().odh_cvt_encode16(code, src, x.data_ptr(), scales.data_ptr(), out.data_ptr(), rows, k,
+                                               _stream_ptr(x.device)))
+        return out
     _check(load_library().odh_cvt_encode(code, x.data_ptr(), scales.data_ptr() if scales is not None else None,
                                          out.data_ptr(), rows, k, _stream_ptr(x.device)))
     return out
@@ -1062,12 +1078,22 @@ def mx_quantize(fmt, x):
     * NaN becomes the format's NaN, fp8 0xFF and bf8 0xFE, whatever its sign.  fp4, fp6 and bf6 have no NaN:
       there a NaN becomes the largest code with the input's sign, so these three formats cannot carry a NaN.
 
-    bf16: Inf stays Inf and NaN stays NaN, quieted."""
+    bf16: Inf stays Inf and NaN stays NaN, quieted.
+
+    ``x`` may be bfloat16 or float16 for the scaled formats.  The result is, byte for byte, ``mx_quantize(fmt,
+    x.float())``: the rule above applied to the exactly widened values, float16 and bfloat16 subnormals included.
+    No float32 copy is made: amax, scale and clamp work on the 16-bit patterns and the codes come from the
+    converters that read 16-bit sources, the 6-bit formats regrouped through LDS.  ``"bf16"`` of a 16-bit ``x``
+    is refused."""
     import torch
 
-    code, rows, k = _cvt_rows(fmt, x)
+    code, src, rows, k = _cvt_rows(fmt, x)
     out = _cvt_out(code, x, rows, k)
     scales = None if code == ODH_CVT_BF16 else torch.empty((rows, k // 32), dtype=torch.uint8, device=x.device)
+    if src != ODH_DCVT_F32:
+        _check(load_library().odh_cvt_quantize16(code, src, x.data_ptr(), out.data_ptr(), scales.data_ptr(), rows, k,
+                                                 _stream_ptr(x.device)))
+        return out, scales
     _check(load_library().odh_cvt_quantize(code, x.data_ptr(), out.data_ptr(),
                                            scales.data_ptr() if scales is not None else None, rows, k,
                                            _stream_ptr(x.device)))
